@@ -10,7 +10,19 @@ config (config/tiger/amazon/tiger.gin: d_model 128 -> attn 384, 6 heads,
 iteration, DDP over RCCL/xGMI for N>1 (weak scaling: per-GPU batch fixed).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+                       [--dump-outputs DIR] [--full]
 For N>1 the driver launches via torch.distributed.run with one rank per GPU.
+
+A plain run sets up, warms up, times exactly --steps steps and prints the
+result line. --dump-outputs DIR additionally writes what the last timed
+step produced (loss, gradients, updated fp32 parameters) as DIR/<name>.npy
+so two builds can be compared output for output. On the GPU that step
+starts from the model/optimizer/RNG state reached after the --warmup steps
+(restored with the clock stopped): the inputs, the initial weights and
+that state depend only on the arguments, while a state reached through
+hundreds of training steps would not be repeatable beyond rounding.
+--full is reserved for measurements beyond the headline figure; the
+flagship benchmark has none, so it changes nothing.
 """
 
 from __future__ import annotations
@@ -59,6 +71,30 @@ def _enable_tuned_gemms() -> None:
         os.environ.setdefault("PYTORCH_TUNABLEOP_FILENAME", csv)
 
 
+# --dump-outputs: at most this many elements per array (3 arrays of fp32
+# => <= 48 MB in all); larger arrays are cut to a fixed seeded sample.
+_DUMP_MAX_ELEMS = 4 * 1024 * 1024
+
+
+def _dump_array(path: str, t: torch.Tensor) -> None:
+    import numpy as np
+
+    a = t.detach().reshape(-1).float().cpu().numpy()
+    if a.size > _DUMP_MAX_ELEMS:
+        idx = np.random.default_rng(0).choice(a.size, _DUMP_MAX_ELEMS,
+                                              replace=False)
+        a = a[np.sort(idx)]
+    np.save(path, np.ascontiguousarray(a, dtype=np.float32))
+
+
+def dump_outputs(out_dir: str, loss, grads, params) -> None:
+    """Write the last timed step's results as float32 .npy files."""
+    os.makedirs(out_dir, exist_ok=True)
+    _dump_array(os.path.join(out_dir, "loss.npy"), loss)
+    _dump_array(os.path.join(out_dir, "grads.npy"), grads)
+    _dump_array(os.path.join(out_dir, "params.npy"), params)
+
+
 def main() -> None:
     _enable_tuned_gemms()
     p = argparse.ArgumentParser()
@@ -66,6 +102,12 @@ def main() -> None:
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--batch-size", type=int, default=256)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's loss, gradients and "
+                        "updated parameters to DIR/<name>.npy (float32)")
+    p.add_argument("--full", action="store_true",
+                   help="also run measurements beyond the headline figure "
+                        "(this benchmark has none)")
     args = p.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -117,11 +159,11 @@ def main() -> None:
         use_graph = runner.captured
         nocopy = os.environ.get("GENREC_BENCH_NOCOPY", "0") == "1"
 
-        def step(i: int) -> None:
+        def step(i: int):
             if nocopy and runner.captured:
                 runner._graph.replay()
-                return
-            runner.step(batches[i % len(batches)])
+                return runner._loss
+            return runner.step(batches[i % len(batches)])
     else:  # CPU path (driver's no-GPU contract check)
         from genrec_amd.parallel import GradReducer
 
@@ -129,7 +171,7 @@ def main() -> None:
                                 weight_decay=0.035)
         reducer = GradReducer(model)
 
-        def step(i: int) -> None:
+        def step(i: int):
             b = batches[i % len(batches)]
             opt.zero_grad(set_to_none=False)
             out = model(**b)
@@ -137,10 +179,25 @@ def main() -> None:
             reducer.finalize()
             torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)
             opt.step()
+            return out.loss
 
     model.train()
     for i in range(args.warmup):
         step(i)
+    if use_gpu:
+        # Training is chaotic: the step is not bitwise repeatable (a rare
+        # one-ulp difference between runs, as float atomics give), and
+        # hundreds of AdamW steps amplify that far beyond rounding
+        # (measured: loss 13% apart after 1000 steps, one parameter 1 ulp
+        # apart after 25). So that the LAST timed step computes
+        # the same thing in every run, the model/optimizer/RNG state of
+        # this point (it depends only on the arguments) is kept here and
+        # put back, with the clock stopped, just before that step.
+        from genrec_amd.ops.attention import _seed_counter
+
+        torch.cuda.synchronize()
+        state0 = (runner._opt_snapshot(), _seed_counter(device).clone(),
+                  torch.cuda.get_rng_state(device), torch.get_rng_state())
     # Extra UNTIMED warmup until GPU clocks settle: a fresh box ramps
     # sclk over the first ~2 s of load; short driver settings (warmup 5)
     # otherwise time the ramp. The timed region below is still exactly
@@ -168,12 +225,40 @@ def main() -> None:
     if use_gpu:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for i in range(args.steps):
+    for i in range(args.steps - 1):
         step(args.warmup + i)
+    elapsed = 0.0
+    if use_gpu:
+        # stop the clock, restore the kept state, restart the clock: the
+        # last step is timed like the others and args.steps steps are
+        # timed in all
+        torch.cuda.synchronize()
+        elapsed = time.perf_counter() - t0
+        runner._opt_restore(state0[0])
+        _seed_counter(device).copy_(state0[1])
+        torch.cuda.set_rng_state(state0[2], device)
+        torch.set_rng_state(state0[3])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+    loss = step(args.warmup + args.steps - 1)
     if use_gpu:
         torch.cuda.synchronize()
     ctx.barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed += time.perf_counter() - t0
+
+    if args.dump_outputs and rank == 0:
+        with torch.no_grad():
+            if use_gpu:
+                params = runner.flat_master if runner.fused else \
+                    torch.cat([m.reshape(-1) for m in runner.masters])
+                grads = runner.flat_grads
+            else:
+                ps = list(model.parameters())
+                params = torch.cat([q.reshape(-1) for q in ps])
+                grads = torch.cat([
+                    (q.grad if q.grad is not None else torch.zeros_like(q))
+                    .reshape(-1) for q in ps])
+            dump_outputs(args.dump_outputs, loss, grads, params)
 
     # MAX over ranks
     if world > 1:

@@ -218,35 +218,37 @@ def test_utils_decorators_and_debug_metrics():
 
 def test_reference_gin_binding_names_are_drop_in():
     """Every `train.X` binding in the REFERENCE's shipped configs must be
-    a parameter of the corresponding trainer here (config drop-in)."""
+    a parameter of the corresponding trainer here (config drop-in). The
+    binding names of each reference config are stored, in file order, in
+    tests/golden/reference_train_bindings.json."""
     import inspect
-    import re
+    import json
 
     from genrec_amd.trainers import (hstu_trainer, lcrec_trainer,
                                      rqvae_trainer, sasrec_trainer,
                                      tiger_trainer)
 
-    ref = "/root/reference/config"
-    if not os.path.isdir(ref):
-        import pytest
-
-        pytest.skip("reference configs not mounted")
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                          "golden", "reference_train_bindings.json")
+    with open(golden) as fh:
+        bindings = json.load(fh)
     cases = {
-        sasrec_trainer: [f"{ref}/sasrec/amazon.gin"],
-        hstu_trainer: [f"{ref}/hstu/amazon.gin"],
-        rqvae_trainer: [f"{ref}/tiger/amazon/rqvae.gin",
-                        f"{ref}/lcrec/amazon/rqvae.gin"],
-        tiger_trainer: [f"{ref}/tiger/amazon/tiger.gin"],
-        lcrec_trainer: [f"{ref}/lcrec/amazon/lcrec.gin",
-                        f"{ref}/lcrec/amazon/lcrec_debug.gin"],
+        sasrec_trainer: ["sasrec/amazon.gin"],
+        hstu_trainer: ["hstu/amazon.gin"],
+        rqvae_trainer: ["tiger/amazon/rqvae.gin",
+                        "lcrec/amazon/rqvae.gin"],
+        tiger_trainer: ["tiger/amazon/tiger.gin"],
+        lcrec_trainer: ["lcrec/amazon/lcrec.gin",
+                        "lcrec/amazon/lcrec_debug.gin"],
     }
+    assert sorted(f for fs in cases.values() for f in fs) == sorted(bindings)
     for mod, files in cases.items():
         params = set(inspect.signature(mod.train.__wrapped__).parameters)
         for f in files:
-            for line in open(f):
-                m = re.match(r"\s*train\.(\w+)\s*=", line)
-                assert not m or m.group(1) in params, \
-                    f"{mod.__name__} missing param {m.group(1)} ({f})"
+            assert bindings[f], f
+            for name in bindings[f]:
+                assert name in params, \
+                    f"{mod.__name__} missing param {name} ({f})"
 
 
 def test_circular_include_raises(tmp_path):

@@ -13,6 +13,15 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 
+@pytest.fixture(autouse=True)
+def _cpu_only_workers(monkeypatch):
+    """These tests are about the gloo/CPU path: the spawned ranks inherit
+    an environment that hides any GPU, so they run the same way on a
+    machine that has one (two ranks cannot share a single device)."""
+    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "-1")
+    monkeypatch.setenv("CUDA_VISIBLE_DEVICES", "-1")
+
+
 def _run_gradreducer(rank, world, port, results):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
