@@ -129,9 +129,10 @@ def bench_rqvae(device, steps, warmup):
                 ms_per_step=el / steps * 1e3)
 
 
-def bench_lcrec(device, steps, warmup, full_size=False):
+def bench_lcrec(device, steps, warmup, full_size=False, attn_impl="sdpa"):
     """LCRec SFT step: Qwen2-1.5B-shaped backbone (lcrec/amazon/lcrec.gin:
-    B=32, L=512, bf16, grad ckpt) — full size only on GPU."""
+    B=32, L=512, bf16, grad ckpt) — full size only on GPU. attn_impl selects
+    the backbone attention ("sdpa" | "genrec_gqa") for same-box A/Bs."""
     from genrec_amd.models.lcrec import LCRec, default_qwen_config
 
     torch.manual_seed(0)
@@ -139,7 +140,7 @@ def bench_lcrec(device, steps, warmup, full_size=False):
     cfg = default_qwen_config() if full_size else default_qwen_config(
         vocab_size=2048, hidden_size=256, num_layers=4, num_heads=8,
         num_kv_heads=2, intermediate_size=512)
-    model = LCRec(config=cfg)
+    model = LCRec(config=cfg, attn_implementation=attn_impl)
     model.add_codebook_tokens(5, 256)
     if full_size:
         model.gradient_checkpointing_enable()
@@ -157,11 +158,15 @@ def bench_lcrec(device, steps, warmup, full_size=False):
                         "labels": ids},
                        lambda out: out.loss, device)
 
+    if device.type == "cuda":
+        torch.cuda.reset_peak_memory_stats(device)
     el = _timeit(step, steps, warmup, device)
+    peak = torch.cuda.max_memory_allocated(device) / 2**30 \
+        if device.type == "cuda" else None
     return dict(model="lcrec-qwen2-1.5b" if full_size else "lcrec-tiny",
-                batch=B, seq_len=L, samples_per_s=B * steps / el,
+                attn=attn_impl, batch=B, seq_len=L, samples_per_s=B * steps / el,
                 tokens_per_s=B * L * steps / el,
-                ms_per_step=el / steps * 1e3)
+                ms_per_step=el / steps * 1e3, peak_hbm_gib=peak)
 
 
 def bench_cobra(device, steps, warmup):
@@ -201,6 +206,8 @@ def main():
     p.add_argument("--steps", type=int, default=30)
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--lcrec-full", action="store_true")
+    p.add_argument("--lcrec-attn", choices=["sdpa", "genrec_gqa"],
+                   default="sdpa")
     p.add_argument("--out", default=None)
     args = p.parse_args()
     device = torch.device("cuda:0") if torch.cuda.is_available() \
@@ -211,6 +218,7 @@ def main():
         kw = {}
         if name == "lcrec":
             kw["full_size"] = args.lcrec_full
+            kw["attn_impl"] = args.lcrec_attn
         try:
             r = BENCHES[name](device, args.steps, args.warmup, **kw)
         except Exception as e:  # keep other models running

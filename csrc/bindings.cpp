@@ -106,6 +106,14 @@ std::vector<torch::Tensor> attn_bwd_flash(
     torch::Tensor drop_mask, c10::optional<torch::Tensor> query_mask,
     double scale, double dropout_p, bool bias_grad, int64_t bias_dim);
 
+std::vector<torch::Tensor> gqa_attn_fwd(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    c10::optional<torch::Tensor> key_pad, double scale, bool causal);
+std::vector<torch::Tensor> gqa_attn_bwd(
+    torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    torch::Tensor out, torch::Tensor lse,
+    c10::optional<torch::Tensor> key_pad, double scale, bool causal);
+
 }  // namespace genrec
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -157,4 +165,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "flash-tiled attention fwd (staged; GENREC_ATTN_FLASH=1)");
   m.def("attn_bwd_flash", &genrec::attn_bwd_flash,
         "flash-tiled attention bwd (staged; GENREC_ATTN_FLASH=1)");
+  m.def("gqa_attn_fwd", &genrec::gqa_attn_fwd,
+        "grouped-query flash attention fwd (D 64/128) -> (out, lse)");
+  m.def("gqa_attn_bwd", &genrec::gqa_attn_bwd,
+        "grouped-query flash attention bwd (deterministic) -> (dq, dk, dv)");
 }

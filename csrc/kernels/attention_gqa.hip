@@ -1,0 +1,824 @@
+// Grouped-query flash attention (bf16, softmax, D in {64,128}) for the
+// Qwen2 backbone of LCRec / NoteLLM.
+//
+// Same fragment geometry as attention_flash.hip (64-row tiles, four waves
+// that own 16 query rows each, v_mfma_f32_16x16x32_bf16, XOR-swizzled LDS
+// tiles read with 16-byte fragment loads, in-register 8x8 transpose for
+// the transposed operands), with what the LLM case needs on top:
+//
+//   * query head h reads KV head h / g in-kernel (g = Hq / Hkv); K/V are
+//     never expanded
+//   * causal masking carries the offset Lk - Lq (prefill, cached decode,
+//     chunked decode); K tiles wholly beyond the diagonal are skipped
+//   * masking is exact (-inf): a masked key has probability 0, a row with
+//     no visible key yields out = 0, lse = 0 and zero gradients
+//   * forward saves only out + lse (O(L)); backward recomputes S per tile
+//   * backward is two kernels without float atomics, so it is bitwise
+//     run-to-run deterministic:
+//       - gqa_bwd_dkdv: one block per (b, kv head, K tile); loops the g
+//         query heads of the group in fixed order and their Q tiles,
+//         accumulating dK/dV in registers
+//       - gqa_bwd_dq: one block per (b, q head, Q tile); loops K tiles
+//     delta = rowsum(dO * O) comes from a small pre-kernel.
+//
+// Layouts: q/k/v are [B,H,L,D] views with d innermost (any 8-element
+// aligned batch/head/row strides, so [B,L,H,D] transposes and contiguous
+// KV caches go through without a copy). out is [B,Lq,Hq,D] contiguous;
+// dq/dk/dv are allocated [B,L,H,D] contiguous and returned as [B,H,L,D]
+// transpose views, which is the layout the projection GEMMs' grads want.
+
+#include <torch/extension.h>
+#include <ATen/hip/HIPContext.h>
+
+#include "../core/common.h"
+
+namespace genrec {
+
+namespace {
+
+constexpr int GT = 64;  // tile rows (queries and keys)
+
+// LDS is accessed through may_alias types: tiles are written with one
+// vector width and read back with another.
+typedef __attribute__((ext_vector_type(8))) short g_short8;
+typedef __attribute__((ext_vector_type(4))) short g_short4;
+typedef __attribute__((ext_vector_type(4))) float g_float4;
+typedef g_short8 __attribute__((may_alias)) g_short8a;
+typedef g_short4 __attribute__((may_alias)) g_short4a;
+typedef short __attribute__((may_alias)) g_short1a;
+
+// XOR swizzle on 16-byte slots; rs = row stride in bytes (128 or 256).
+__device__ __forceinline__ int gswz(int row, int byte_in_row, int rs) {
+  return row * rs + (byte_in_row ^ ((row & 7) << 4));
+}
+
+__device__ __forceinline__ g_short8 gfrag(const char* base, int row0, int k0,
+                                          int lane, int rs) {
+  int row = row0 + (lane & 15);
+  int byte = (k0 + ((lane >> 4) << 3)) * 2;
+  return *reinterpret_cast<const g_short8a*>(base + gswz(row, byte, rs));
+}
+
+// In-register 8x8 transpose across the 8 lanes {lane ^ 8, ^ 16, ^ 32} (as
+// xpose8x8 in attention_flash.hip). A variant that exchanges only the four
+// replaced elements per stage, packed two per shuffle, measured slower.
+__device__ __forceinline__ void gxpose8x8(short (&vals)[8], int g) {
+#pragma unroll
+  for (int m = 1; m < 8; m <<= 1) {
+    short nv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      int t = __shfl_xor((int)vals[e ^ m], 8 * m, 64);
+      nv[e] = ((e & m) != (g & m)) ? (short)t : vals[e];
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) vals[e] = nv[e];
+  }
+}
+
+__device__ __forceinline__ short bf16_bits(float x) {
+  __hip_bfloat16 h = __float2bfloat16(x);
+  return *reinterpret_cast<short*>(&h);
+}
+
+// Stage 64 rows x D of a [*, L, D]-strided operand (row stride sl) into a
+// natural tile nat[64][D] and/or a transposed tile tr[D][64]. Rows at or
+// beyond L are zero. Items are walked in 64-wide column halves so that the
+// 8 lanes (lane>>3)&7 of a wave hold 8 consecutive rows of one 8-column
+// chunk, which is what the in-register transpose needs. Every thread runs
+// the same number of iterations (shuffles inside).
+template <int D, bool NAT, bool TR>
+__device__ __forceinline__ void gstage(const __hip_bfloat16* __restrict__ src,
+                                       int64_t sl, int r0, int L, char* nat,
+                                       char* tr, int tid) {
+  const int lane = tid & 63;
+  for (int idx = tid; idx < GT * (D / 8); idx += 256) {
+    int half = idx >> 9;          // 512 items per 64-column half
+    int rem = idx & 511;
+    int row = rem >> 3;
+    int d0 = half * 64 + (rem & 7) * 8;
+    int gi = r0 + row;
+    g_short8 val = {};
+    if (gi < L) {
+      val = *reinterpret_cast<const g_short8*>(&src[(int64_t)gi * sl + d0]);
+    }
+    if (NAT) {
+      *reinterpret_cast<g_short8a*>(nat + gswz(row, d0 * 2, D * 2)) = val;
+    }
+    if (TR) {
+      const int g = (lane >> 3) & 7;  // == row & 7
+      short t[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) t[e] = val[e];
+      gxpose8x8(t, g);
+      g_short8 pack;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) pack[e] = t[e];
+      *reinterpret_cast<g_short8a*>(tr + gswz(d0 + g, (row & ~7) * 2, 128)) =
+          pack;
+    }
+  }
+}
+
+// ------------------------------------------------------------------ forward
+
+template <int D>
+__global__ void __launch_bounds__(256)
+gqa_fwd_kernel(const __hip_bfloat16* __restrict__ q,
+               const __hip_bfloat16* __restrict__ k,
+               const __hip_bfloat16* __restrict__ v,
+               const bool* __restrict__ key_pad,  // null | [B,Lk]
+               __hip_bfloat16* __restrict__ out,  // [B,Lq,Hq,D]
+               float* __restrict__ lse,           // [B,Hq,Lq]
+               int Hq, int Hkv, int Lq, int Lk, float scale, bool causal,
+               int64_t q_sb, int64_t q_sh, int64_t q_sl,
+               int64_t k_sb, int64_t k_sh, int64_t k_sl,
+               int64_t v_sb, int64_t v_sh, int64_t v_sl) {
+  constexpr int RS = D * 2;
+  const int b = blockIdx.x / Hq, h = blockIdx.x % Hq;
+  const int hk = h / (Hq / Hkv);
+  const int q0 = blockIdx.y * GT;
+  const int off = Lk - Lq;  // query row i sits at absolute position i + off
+
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* qs = smem;             // [64][D]   Q rows
+  char* ks = qs + GT * RS;     // [64][D]   K rows (per tile)
+  char* vt = ks + GT * RS;     // [D][64]   V^T (per tile)
+  char* ps = vt + D * 128;     // [64][64]  P (per tile)
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int col_base = lane & 15;
+  const int row_grp = (lane >> 4) << 2;
+  const int strip = wid * 16;
+
+  gstage<D, true, false>(q + (int64_t)b * q_sb + (int64_t)h * q_sh, q_sl, q0,
+                         Lq, qs, nullptr, tid);
+
+  float m_row[4], l_row[4];
+  g_float4 accO[D / 16];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) { m_row[r] = -INFINITY; l_row[r] = 0.f; }
+#pragma unroll
+  for (int f = 0; f < D / 16; ++f) accO[f] = g_float4{0, 0, 0, 0};
+
+  // K tiles wholly beyond the diagonal of this Q tile are skipped
+  int kt_end = Lk;
+  if (causal) kt_end = min(Lk, q0 + GT + off);
+  const __hip_bfloat16* kb = k + (int64_t)b * k_sb + (int64_t)hk * k_sh;
+  const __hip_bfloat16* vb = v + (int64_t)b * v_sb + (int64_t)hk * v_sh;
+
+  for (int kt0 = 0; kt0 < kt_end; kt0 += GT) {
+    __syncthreads();  // previous iteration's ks/vt fully consumed
+    gstage<D, true, false>(kb, k_sl, kt0, Lk, ks, nullptr, tid);
+    gstage<D, false, true>(vb, v_sl, kt0, Lk, nullptr, vt, tid);
+    __syncthreads();
+
+    // ---- S = Q K_t^T
+    g_float4 acc[4];
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+      acc[f] = g_float4{0, 0, 0, 0};
+#pragma unroll
+      for (int kk = 0; kk < D; kk += 32) {
+        acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            gfrag(qs, strip, kk, lane, RS), gfrag(ks, f * 16, kk, lane, RS),
+            acc[f], 0, 0, 0);
+      }
+    }
+
+    // ---- exact masking (-inf)
+    float s_val[4][4];
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+      int j = kt0 + f * 16 + col_base;
+      bool jok = j < Lk;
+      if (jok && key_pad) jok = !key_pad[(int64_t)b * Lk + j];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        int i = q0 + strip + row_grp + r;
+        bool ok = jok && i < Lq && !(causal && j > i + off);
+        s_val[f][r] = ok ? __fmul_rn(acc[f][r], scale) : -INFINITY;
+      }
+    }
+
+    // ---- running softmax; a row whose keys so far are all masked keeps
+    // m = -inf, l = 0 and contributes nothing (no exp(-inf - -inf))
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float tmax = fmaxf(fmaxf(s_val[0][r], s_val[1][r]),
+                         fmaxf(s_val[2][r], s_val[3][r]));
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1)
+        tmax = fmaxf(tmax, __shfl_xor(tmax, o, 64));
+      float m_new = fmaxf(m_row[r], tmax);
+      bool dead = (m_new == -INFINITY);
+      float a = (dead || m_row[r] == -INFINITY) ? (dead ? 1.f : 0.f)
+                                                : __expf(m_row[r] - m_new);
+      float sum = 0.f;
+#pragma unroll
+      for (int f = 0; f < 4; ++f) {
+        float p = (s_val[f][r] == -INFINITY) ? 0.f
+                                             : __expf(s_val[f][r] - m_new);
+        s_val[f][r] = p;  // reuse as unnormalized p
+        sum += p;
+      }
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) sum += __shfl_xor(sum, o, 64);
+      l_row[r] = l_row[r] * a + sum;
+      m_row[r] = m_new;
+#pragma unroll
+      for (int f = 0; f < D / 16; ++f) accO[f][r] *= a;
+    }
+
+    // ---- stash P (this wave's 16 rows only)
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        int row = strip + row_grp + r;
+        *reinterpret_cast<g_short1a*>(
+            ps + gswz(row, (f * 16 + col_base) * 2, 128)) =
+            bf16_bits(s_val[f][r]);
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+
+    // ---- accO += P V_t
+#pragma unroll
+    for (int f = 0; f < D / 16; ++f) {
+#pragma unroll
+      for (int kk = 0; kk < GT; kk += 32) {
+        accO[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            gfrag(ps, strip, kk, lane, 128), gfrag(vt, f * 16, kk, lane, 128),
+            accO[f], 0, 0, 0);
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+
+  // ---- finalize
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    int i = q0 + strip + row_grp + r;
+    if (i >= Lq) continue;
+    float inv = (l_row[r] > 0.f) ? 1.0f / l_row[r] : 0.f;
+    int64_t ob = (((int64_t)b * Lq + i) * Hq + h) * D;
+#pragma unroll
+    for (int f = 0; f < D / 16; ++f) {
+      out[ob + f * 16 + col_base] = __float2bfloat16(accO[f][r] * inv);
+    }
+    if (col_base == 0) {
+      lse[((int64_t)b * Hq + h) * Lq + i] =
+          (l_row[r] > 0.f) ? m_row[r] + __logf(l_row[r]) : 0.f;
+    }
+  }
+}
+
+// ------------------------------------------------- delta = rowsum(dO * O)
+
+template <int D>
+__global__ void __launch_bounds__(256)
+gqa_delta_kernel(const __hip_bfloat16* __restrict__ dout,  // [B,Lq,Hq,D] view
+                 const __hip_bfloat16* __restrict__ out,   // [B,Lq,Hq,D]
+                 float* __restrict__ delta,                // [B,Hq,Lq]
+                 int Hq, int Lq, int64_t n_rows,
+                 int64_t do_sb, int64_t do_sh, int64_t do_sl) {
+  constexpr int GRP = D / 8;  // lanes per row
+  const int64_t row = (int64_t)blockIdx.x * (256 / GRP) + threadIdx.x / GRP;
+  const int c = (threadIdx.x % GRP) * 8;
+  float acc = 0.f;
+  if (row < n_rows) {
+    int i = row % Lq;
+    int64_t bh = row / Lq;
+    int h = bh % Hq;
+    int64_t b = bh / Hq;
+    g_short8 a = *reinterpret_cast<const g_short8*>(
+        &dout[b * do_sb + (int64_t)h * do_sh + (int64_t)i * do_sl + c]);
+    g_short8 o = *reinterpret_cast<const g_short8*>(
+        &out[((b * Lq + i) * Hq + h) * D + c]);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      acc += __uint_as_float(((unsigned int)(unsigned short)a[e]) << 16) *
+             __uint_as_float(((unsigned int)(unsigned short)o[e]) << 16);
+    }
+  }
+#pragma unroll
+  for (int o = 1; o < GRP; o <<= 1) acc += __shfl_xor(acc, o, 64);
+  if (row < n_rows && c == 0) delta[row] = acc;
+}
+
+// Recompute P and dS for one 16x64 strip from the S and dP accumulators.
+// p = exp(s - lse) for visible keys, exactly 0 for masked ones. The
+// softmax Jacobian carries p (1 - p): a probability that rounds to 1 (a row
+// with one visible key, e.g. row 0 of every prefill) has dS = 0, where
+// dP - delta would leave the rounding difference between the MFMA dot
+// product and the delta pre-kernel's sum.
+#define GQA_P_DS(f, r, p_out, ds_out)                                      \
+  {                                                                        \
+    int i_ = q0 + strip + row_grp + (r);                                   \
+    bool ok_ = jok[f] && i_ < Lq && !(causal && jcol[f] > i_ + off);       \
+    float s_ = __fmul_rn(acc[f][r], scale); /* as forward: no fma */       \
+    float p_ = ok_ ? __expf(s_ - lse_r[r]) : 0.f;                          \
+    p_out = p_;                                                            \
+    ds_out = (p_ == 1.0f) ? 0.f : p_ * (accp[f][r] - dl_r[r]) * scale;     \
+  }
+
+// ------------------------------------------------------- backward: dK, dV
+
+template <int D>
+__global__ void __launch_bounds__(256)
+gqa_bwd_dkdv_kernel(const __hip_bfloat16* __restrict__ dout,
+                    const __hip_bfloat16* __restrict__ q,
+                    const __hip_bfloat16* __restrict__ k,
+                    const __hip_bfloat16* __restrict__ v,
+                    const float* __restrict__ lse,    // [B,Hq,Lq]
+                    const float* __restrict__ delta,  // [B,Hq,Lq]
+                    const bool* __restrict__ key_pad,
+                    __hip_bfloat16* __restrict__ dk,  // [B,Lk,Hkv,D]
+                    __hip_bfloat16* __restrict__ dv,  // [B,Lk,Hkv,D]
+                    int Hq, int Hkv, int Lq, int Lk, float scale, bool causal,
+                    int64_t do_sb, int64_t do_sh, int64_t do_sl,
+                    int64_t q_sb, int64_t q_sh, int64_t q_sl,
+                    int64_t k_sb, int64_t k_sh, int64_t k_sl,
+                    int64_t v_sb, int64_t v_sh, int64_t v_sl) {
+  constexpr int RS = D * 2;
+  const int b = blockIdx.x / Hkv, hk = blockIdx.x % Hkv;
+  const int grp = Hq / Hkv;
+  const int kt0 = blockIdx.y * GT;
+  const int off = Lk - Lq;
+
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* ks = smem;              // [64][D]  K_t rows (persistent)
+  char* vs = ks + GT * RS;      // [64][D]  V_t rows (persistent)
+  char* qs = vs + GT * RS;      // [64][D]  Q rows (per q-tile)
+  char* dos = qs + GT * RS;     // [64][D]  dO rows (per q-tile)
+  char* qt = dos + GT * RS;     // [D][64]  Q^T
+  char* dot = qt + D * 128;     // [D][64]  dO^T
+  char* dst = dot + D * 128;    // [64 j][64 i]  (scale*dS)^T
+  char* pt = dst + GT * 128;    // [64 j][64 i]  P^T
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int col_base = lane & 15;
+  const int row_grp = (lane >> 4) << 2;
+  const int strip = wid * 16;
+  const int i0g = strip + row_grp;  // 8-byte aligned store base
+
+  gstage<D, true, false>(k + (int64_t)b * k_sb + (int64_t)hk * k_sh, k_sl,
+                         kt0, Lk, ks, nullptr, tid);
+  gstage<D, true, false>(v + (int64_t)b * v_sb + (int64_t)hk * v_sh, v_sl,
+                         kt0, Lk, vs, nullptr, tid);
+
+  int jcol[4];
+  bool jok[4];
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    jcol[f] = kt0 + f * 16 + col_base;
+    jok[f] = jcol[f] < Lk;
+    if (jok[f] && key_pad) jok[f] = !key_pad[(int64_t)b * Lk + jcol[f]];
+  }
+
+  g_float4 acck[D / 16], accv[D / 16];
+#pragma unroll
+  for (int f = 0; f < D / 16; ++f) {
+    acck[f] = g_float4{0, 0, 0, 0};
+    accv[f] = g_float4{0, 0, 0, 0};
+  }
+
+  // Q tiles whose every row sits before this K tile see none of it
+  int q_begin = 0;
+  if (causal && kt0 - off > 0) q_begin = ((kt0 - off) / GT) * GT;
+
+  for (int hh = 0; hh < grp; ++hh) {
+    const int h = hk * grp + hh;
+    const __hip_bfloat16* qb = q + (int64_t)b * q_sb + (int64_t)h * q_sh;
+    const __hip_bfloat16* dob = dout + (int64_t)b * do_sb + (int64_t)h * do_sh;
+    const int64_t rowb = ((int64_t)b * Hq + h) * Lq;
+    for (int q0 = q_begin; q0 < Lq; q0 += GT) {
+      __syncthreads();  // previous tile's qs/dos/qt/dot/dst/pt consumed
+      gstage<D, true, true>(qb, q_sl, q0, Lq, qs, qt, tid);
+      gstage<D, true, true>(dob, do_sl, q0, Lq, dos, dot, tid);
+      __syncthreads();
+
+      float lse_r[4], dl_r[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        int i = q0 + strip + row_grp + r;
+        lse_r[r] = i < Lq ? lse[rowb + i] : 0.f;
+        dl_r[r] = i < Lq ? delta[rowb + i] : 0.f;
+      }
+
+      // ---- S = Q K_t^T, dP = dO V_t^T (rows = this wave's q strip)
+      g_float4 acc[4], accp[4];
+#pragma unroll
+      for (int f = 0; f < 4; ++f) {
+        acc[f] = g_float4{0, 0, 0, 0};
+        accp[f] = g_float4{0, 0, 0, 0};
+#pragma unroll
+        for (int kk = 0; kk < D; kk += 32) {
+          acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              gfrag(qs, strip, kk, lane, RS), gfrag(ks, f * 16, kk, lane, RS),
+              acc[f], 0, 0, 0);
+          accp[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              gfrag(dos, strip, kk, lane, RS),
+              gfrag(vs, f * 16, kk, lane, RS), accp[f], 0, 0, 0);
+        }
+      }
+
+      // ---- P^T and (scale*dS)^T tiles
+#pragma unroll
+      for (int f = 0; f < 4; ++f) {
+        g_short4 ppack, dpack;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float pv, dsv;
+          GQA_P_DS(f, r, pv, dsv);
+          ppack[r] = bf16_bits(pv);
+          dpack[r] = bf16_bits(dsv);
+        }
+        int jl = f * 16 + col_base;
+        *reinterpret_cast<g_short4a*>(pt + gswz(jl, i0g * 2, 128)) = ppack;
+        *reinterpret_cast<g_short4a*>(dst + gswz(jl, i0g * 2, 128)) = dpack;
+      }
+      __syncthreads();  // pt/dst complete across waves
+
+      // ---- dK_t += (scale*dS)^T Q ; dV_t += P^T dO (rows = k strip)
+#pragma unroll
+      for (int f = 0; f < D / 16; ++f) {
+#pragma unroll
+        for (int kk = 0; kk < GT; kk += 32) {
+          acck[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              gfrag(dst, strip, kk, lane, 128),
+              gfrag(qt, f * 16, kk, lane, 128), acck[f], 0, 0, 0);
+          accv[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              gfrag(pt, strip, kk, lane, 128),
+              gfrag(dot, f * 16, kk, lane, 128), accv[f], 0, 0, 0);
+        }
+      }
+    }
+  }
+
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    int j = kt0 + strip + row_grp + r;
+    if (j >= Lk) continue;
+    int64_t ob = (((int64_t)b * Lk + j) * Hkv + hk) * D;
+#pragma unroll
+    for (int f = 0; f < D / 16; ++f) {
+      dk[ob + f * 16 + col_base] = __float2bfloat16(acck[f][r]);
+      dv[ob + f * 16 + col_base] = __float2bfloat16(accv[f][r]);
+    }
+  }
+}
+
+// ----------------------------------------------------------- backward: dQ
+
+template <int D>
+__global__ void __launch_bounds__(256)
+gqa_bwd_dq_kernel(const __hip_bfloat16* __restrict__ dout,
+                  const __hip_bfloat16* __restrict__ q,
+                  const __hip_bfloat16* __restrict__ k,
+                  const __hip_bfloat16* __restrict__ v,
+                  const float* __restrict__ lse,
+                  const float* __restrict__ delta,
+                  const bool* __restrict__ key_pad,
+                  __hip_bfloat16* __restrict__ dq,  // [B,Lq,Hq,D]
+                  int Hq, int Hkv, int Lq, int Lk, float scale, bool causal,
+                  int64_t do_sb, int64_t do_sh, int64_t do_sl,
+                  int64_t q_sb, int64_t q_sh, int64_t q_sl,
+                  int64_t k_sb, int64_t k_sh, int64_t k_sl,
+                  int64_t v_sb, int64_t v_sh, int64_t v_sl) {
+  constexpr int RS = D * 2;
+  const int b = blockIdx.x / Hq, h = blockIdx.x % Hq;
+  const int hk = h / (Hq / Hkv);
+  const int q0 = blockIdx.y * GT;
+  const int off = Lk - Lq;
+
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* qs = smem;              // [64][D]  Q rows (persistent)
+  char* dos = qs + GT * RS;     // [64][D]  dO rows (persistent)
+  char* ks = dos + GT * RS;     // [64][D]  K_t rows (per tile)
+  char* vs = ks + GT * RS;      // [64][D]  V_t rows (per tile)
+  char* kt = vs + GT * RS;      // [D][64]  K_t^T
+  char* dsn = kt + D * 128;     // [64 i][64 j]  scale*dS
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int col_base = lane & 15;
+  const int row_grp = (lane >> 4) << 2;
+  const int strip = wid * 16;
+
+  gstage<D, true, false>(q + (int64_t)b * q_sb + (int64_t)h * q_sh, q_sl, q0,
+                         Lq, qs, nullptr, tid);
+  gstage<D, true, false>(dout + (int64_t)b * do_sb + (int64_t)h * do_sh,
+                         do_sl, q0, Lq, dos, nullptr, tid);
+
+  const int64_t rowb = ((int64_t)b * Hq + h) * Lq;
+  float lse_r[4], dl_r[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    int i = q0 + strip + row_grp + r;
+    lse_r[r] = i < Lq ? lse[rowb + i] : 0.f;
+    dl_r[r] = i < Lq ? delta[rowb + i] : 0.f;
+  }
+
+  g_float4 accq[D / 16];
+#pragma unroll
+  for (int f = 0; f < D / 16; ++f) accq[f] = g_float4{0, 0, 0, 0};
+
+  int kt_end = Lk;
+  if (causal) kt_end = min(Lk, q0 + GT + off);
+  const __hip_bfloat16* kb = k + (int64_t)b * k_sb + (int64_t)hk * k_sh;
+  const __hip_bfloat16* vb = v + (int64_t)b * v_sb + (int64_t)hk * v_sh;
+
+  for (int kt0 = 0; kt0 < kt_end; kt0 += GT) {
+    __syncthreads();  // previous tile's ks/vs/kt consumed
+    gstage<D, true, true>(kb, k_sl, kt0, Lk, ks, kt, tid);
+    gstage<D, true, false>(vb, v_sl, kt0, Lk, vs, nullptr, tid);
+    __syncthreads();
+
+    int jcol[4];
+    bool jok[4];
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+      jcol[f] = kt0 + f * 16 + col_base;
+      jok[f] = jcol[f] < Lk;
+      if (jok[f] && key_pad) jok[f] = !key_pad[(int64_t)b * Lk + jcol[f]];
+    }
+
+    g_float4 acc[4], accp[4];
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+      acc[f] = g_float4{0, 0, 0, 0};
+      accp[f] = g_float4{0, 0, 0, 0};
+#pragma unroll
+      for (int kk = 0; kk < D; kk += 32) {
+        acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            gfrag(qs, strip, kk, lane, RS), gfrag(ks, f * 16, kk, lane, RS),
+            acc[f], 0, 0, 0);
+        accp[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            gfrag(dos, strip, kk, lane, RS), gfrag(vs, f * 16, kk, lane, RS),
+            accp[f], 0, 0, 0);
+      }
+    }
+
+    // ---- scale*dS rows of this wave's strip
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float pv, dsv;
+        GQA_P_DS(f, r, pv, dsv);
+        (void)pv;
+        int row = strip + row_grp + r;
+        *reinterpret_cast<g_short1a*>(
+            dsn + gswz(row, (f * 16 + col_base) * 2, 128)) = bf16_bits(dsv);
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+
+    // ---- dQ += (scale*dS) K_t
+#pragma unroll
+    for (int f = 0; f < D / 16; ++f) {
+#pragma unroll
+      for (int kk = 0; kk < GT; kk += 32) {
+        accq[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            gfrag(dsn, strip, kk, lane, 128),
+            gfrag(kt, f * 16, kk, lane, 128), accq[f], 0, 0, 0);
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    int i = q0 + strip + row_grp + r;
+    if (i >= Lq) continue;
+    int64_t ob = (((int64_t)b * Lq + i) * Hq + h) * D;
+#pragma unroll
+    for (int f = 0; f < D / 16; ++f) {
+      dq[ob + f * 16 + col_base] = __float2bfloat16(accq[f][r]);
+    }
+  }
+}
+
+#undef GQA_P_DS
+
+// ------------------------------------------------------------------ hosts
+
+bool gqa_ok_strides(const torch::Tensor& t) {
+  return t.stride(3) == 1 && t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0 &&
+         t.stride(2) % 8 == 0 &&
+         reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+
+struct GqaShape {
+  int B, Hq, Hkv, Lq, Lk, D;
+};
+
+GqaShape gqa_check(const torch::Tensor& q, const torch::Tensor& k,
+                   const torch::Tensor& v,
+                   const c10::optional<torch::Tensor>& key_pad) {
+  TORCH_CHECK(q.is_cuda() && k.is_cuda() && v.is_cuda(),
+              "gqa_attn: q/k/v must be GPU tensors");
+  TORCH_CHECK(q.scalar_type() == torch::kBFloat16 &&
+                  k.scalar_type() == torch::kBFloat16 &&
+                  v.scalar_type() == torch::kBFloat16,
+              "gqa_attn: q/k/v must be bfloat16");
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4,
+              "gqa_attn: q/k/v must be [B,H,L,D]");
+  GqaShape s;
+  s.B = q.size(0); s.Hq = q.size(1); s.Lq = q.size(2); s.D = q.size(3);
+  s.Hkv = k.size(1); s.Lk = k.size(2);
+  TORCH_CHECK(s.D == 64 || s.D == 128,
+              "gqa_attn: head dim must be 64 or 128, got ", s.D);
+  TORCH_CHECK(k.size(0) == s.B && k.size(3) == s.D && v.sizes() == k.sizes(),
+              "gqa_attn: k/v must be [B,Hkv,Lk,D] matching q");
+  TORCH_CHECK(s.Hkv >= 1 && s.Hq % s.Hkv == 0,
+              "gqa_attn: Hq (", s.Hq, ") must be a multiple of Hkv (", s.Hkv,
+              ")");
+  TORCH_CHECK(s.B >= 1 && s.Lq >= 1 && s.Lk >= 1,
+              "gqa_attn: empty batch or sequence");
+  TORCH_CHECK((int64_t)(s.Lq + GT - 1) / GT <= 65535 &&
+                  (int64_t)(s.Lk + GT - 1) / GT <= 65535,
+              "gqa_attn: sequence too long");
+  if (key_pad.has_value()) {
+    TORCH_CHECK(key_pad->is_cuda() &&
+                    key_pad->scalar_type() == torch::kBool &&
+                    key_pad->dim() == 2 && key_pad->size(0) == s.B &&
+                    key_pad->size(1) == s.Lk,
+                "gqa_attn: key_pad must be a bool [B,Lk] GPU tensor");
+  }
+  return s;
+}
+
+// Kernels at or above 64 KiB of dynamic LDS raise their limit once.
+template <typename K>
+void gqa_allow_lds(K kernel, size_t smem, bool* done) {
+  if (smem >= 64 * 1024 && !*done) {
+    C10_HIP_CHECK(hipFuncSetAttribute(
+        reinterpret_cast<const void*>(kernel),
+        hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    *done = true;
+  }
+}
+
+constexpr int kMaxDev = 64;
+
+template <int D>
+void gqa_launch_fwd(const GqaShape& s, const torch::Tensor& q,
+                    const torch::Tensor& k, const torch::Tensor& v,
+                    const bool* kp, torch::Tensor& out, torch::Tensor& lse,
+                    float scale, bool causal) {
+  dim3 grid(s.B * s.Hq, (s.Lq + GT - 1) / GT);
+  size_t smem = 2 * GT * D * 2 + D * 128 + GT * 128;
+  static bool done[kMaxDev] = {};
+  gqa_allow_lds(gqa_fwd_kernel<D>, smem, &done[q.get_device() % kMaxDev]);
+  auto stream = at::cuda::getCurrentHIPStream();
+  hipLaunchKernelGGL(gqa_fwd_kernel<D>, grid, dim3(256), smem, stream,
+      reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
+      reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
+      reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()), kp,
+      reinterpret_cast<__hip_bfloat16*>(out.data_ptr()),
+      lse.data_ptr<float>(), s.Hq, s.Hkv, s.Lq, s.Lk, scale, causal,
+      q.stride(0), q.stride(1), q.stride(2),
+      k.stride(0), k.stride(1), k.stride(2),
+      v.stride(0), v.stride(1), v.stride(2));
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+template <int D>
+void gqa_launch_bwd(const GqaShape& s, const torch::Tensor& dout,
+                    const torch::Tensor& q, const torch::Tensor& k,
+                    const torch::Tensor& v, const torch::Tensor& out,
+                    const torch::Tensor& lse, const bool* kp,
+                    torch::Tensor& delta, torch::Tensor& dq,
+                    torch::Tensor& dk, torch::Tensor& dv, float scale,
+                    bool causal) {
+  auto stream = at::cuda::getCurrentHIPStream();
+  const int dev = q.get_device() % kMaxDev;
+  const __hip_bfloat16* dop =
+      reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr());
+  const __hip_bfloat16* qp =
+      reinterpret_cast<const __hip_bfloat16*>(q.data_ptr());
+  const __hip_bfloat16* kp16 =
+      reinterpret_cast<const __hip_bfloat16*>(k.data_ptr());
+  const __hip_bfloat16* vp =
+      reinterpret_cast<const __hip_bfloat16*>(v.data_ptr());
+  // dout is a [B,Lq,Hq,D] view: batch, head, row strides
+  const int64_t do_sb = dout.stride(0), do_sh = dout.stride(2),
+                do_sl = dout.stride(1);
+  {
+    constexpr int rows_per_block = 256 / (D / 8);
+    int64_t n_rows = (int64_t)s.B * s.Hq * s.Lq;
+    dim3 grid((unsigned int)((n_rows + rows_per_block - 1) / rows_per_block));
+    hipLaunchKernelGGL(gqa_delta_kernel<D>, grid, dim3(256), 0, stream, dop,
+        reinterpret_cast<const __hip_bfloat16*>(out.data_ptr()),
+        delta.data_ptr<float>(), s.Hq, s.Lq, n_rows, do_sb, do_sh, do_sl);
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  }
+  {
+    dim3 grid(s.B * s.Hkv, (s.Lk + GT - 1) / GT);
+    size_t smem = 4 * GT * D * 2 + 2 * D * 128 + 2 * GT * 128;
+    static bool done[kMaxDev] = {};
+    gqa_allow_lds(gqa_bwd_dkdv_kernel<D>, smem, &done[dev]);
+    hipLaunchKernelGGL(gqa_bwd_dkdv_kernel<D>, grid, dim3(256), smem, stream,
+        dop, qp, kp16, vp, lse.data_ptr<float>(), delta.data_ptr<float>(),
+        kp, reinterpret_cast<__hip_bfloat16*>(dk.data_ptr()),
+        reinterpret_cast<__hip_bfloat16*>(dv.data_ptr()),
+        s.Hq, s.Hkv, s.Lq, s.Lk, scale, causal, do_sb, do_sh, do_sl,
+        q.stride(0), q.stride(1), q.stride(2),
+        k.stride(0), k.stride(1), k.stride(2),
+        v.stride(0), v.stride(1), v.stride(2));
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  }
+  {
+    dim3 grid(s.B * s.Hq, (s.Lq + GT - 1) / GT);
+    size_t smem = 4 * GT * D * 2 + D * 128 + GT * 128;
+    static bool done[kMaxDev] = {};
+    gqa_allow_lds(gqa_bwd_dq_kernel<D>, smem, &done[dev]);
+    hipLaunchKernelGGL(gqa_bwd_dq_kernel<D>, grid, dim3(256), smem, stream,
+        dop, qp, kp16, vp, lse.data_ptr<float>(), delta.data_ptr<float>(),
+        kp, reinterpret_cast<__hip_bfloat16*>(dq.data_ptr()),
+        s.Hq, s.Hkv, s.Lq, s.Lk, scale, causal, do_sb, do_sh, do_sl,
+        q.stride(0), q.stride(1), q.stride(2),
+        k.stride(0), k.stride(1), k.stride(2),
+        v.stride(0), v.stride(1), v.stride(2));
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  }
+}
+
+}  // namespace
+
+std::vector<torch::Tensor> gqa_attn_fwd(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    c10::optional<torch::Tensor> key_pad, double scale, bool causal) {
+  GqaShape s = gqa_check(q, k, v, key_pad);
+  torch::Tensor qn = gqa_ok_strides(q) ? q : q.contiguous();
+  torch::Tensor kn = gqa_ok_strides(k) ? k : k.contiguous();
+  torch::Tensor vn = gqa_ok_strides(v) ? v : v.contiguous();
+  torch::Tensor kpc;
+  const bool* kp = nullptr;
+  if (key_pad.has_value()) {
+    kpc = key_pad->contiguous();
+    kp = kpc.data_ptr<bool>();
+  }
+  auto out = torch::empty({s.B, s.Lq, s.Hq, s.D}, q.options());
+  auto lse = torch::empty({s.B, s.Hq, s.Lq},
+                          q.options().dtype(torch::kFloat32));
+  if (s.D == 64) {
+    gqa_launch_fwd<64>(s, qn, kn, vn, kp, out, lse, (float)scale, causal);
+  } else {
+    gqa_launch_fwd<128>(s, qn, kn, vn, kp, out, lse, (float)scale, causal);
+  }
+  return {out, lse};
+}
+
+std::vector<torch::Tensor> gqa_attn_bwd(
+    torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    torch::Tensor out, torch::Tensor lse,
+    c10::optional<torch::Tensor> key_pad, double scale, bool causal) {
+  GqaShape s = gqa_check(q, k, v, key_pad);
+  TORCH_CHECK(dout.is_cuda() && dout.scalar_type() == torch::kBFloat16 &&
+                  dout.dim() == 4 && dout.size(0) == s.B &&
+                  dout.size(1) == s.Lq && dout.size(2) == s.Hq &&
+                  dout.size(3) == s.D,
+              "gqa_attn_bwd: dout must be bf16 [B,Lq,Hq,D]");
+  TORCH_CHECK(out.scalar_type() == torch::kBFloat16 &&
+                  out.sizes() == dout.sizes() && out.is_contiguous(),
+              "gqa_attn_bwd: out must be the contiguous forward output");
+  TORCH_CHECK(lse.scalar_type() == torch::kFloat32 && lse.is_contiguous() &&
+                  lse.dim() == 3 && lse.size(0) == s.B &&
+                  lse.size(1) == s.Hq && lse.size(2) == s.Lq,
+              "gqa_attn_bwd: lse must be the fp32 [B,Hq,Lq] forward lse");
+  torch::Tensor don = gqa_ok_strides(dout) ? dout : dout.contiguous();
+  torch::Tensor qn = gqa_ok_strides(q) ? q : q.contiguous();
+  torch::Tensor kn = gqa_ok_strides(k) ? k : k.contiguous();
+  torch::Tensor vn = gqa_ok_strides(v) ? v : v.contiguous();
+  torch::Tensor kpc;
+  const bool* kp = nullptr;
+  if (key_pad.has_value()) {
+    kpc = key_pad->contiguous();
+    kp = kpc.data_ptr<bool>();
+  }
+  auto delta = torch::empty({s.B, s.Hq, s.Lq}, lse.options());
+  // [B,L,H,D] storage, handed back as [B,H,L,D] views: the grads of the
+  // q/k/v projections' .view().transpose(1,2) are then contiguous
+  auto dq = torch::empty({s.B, s.Lq, s.Hq, s.D}, q.options());
+  auto dk = torch::empty({s.B, s.Lk, s.Hkv, s.D}, k.options());
+  auto dv = torch::empty({s.B, s.Lk, s.Hkv, s.D}, v.options());
+  if (s.D == 64) {
+    gqa_launch_bwd<64>(s, don, qn, kn, vn, out, lse, kp, delta, dq, dk, dv,
+                       (float)scale, causal);
+  } else {
+    gqa_launch_bwd<128>(s, don, qn, kn, vn, out, lse, kp, delta, dq, dk, dv,
+                        (float)scale, causal);
+  }
+  return {dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2)};
+}
+
+}  // namespace genrec

@@ -49,16 +49,31 @@ def default_qwen_config(vocab_size: int = 512, hidden_size: int = 1536,
         max_position_embeddings=max_position_embeddings, tie_word_embeddings=True)
 
 
+def _attn_kwargs(attn_implementation: Optional[str]) -> Dict[str, str]:
+    """from_config / from_pretrained kwargs for an attention switch. None
+    passes nothing (the transformers default); "genrec_gqa" is registered
+    by importing genrec_amd.modules.hf_attention."""
+    if attn_implementation is None:
+        return {}
+    from genrec_amd.modules import hf_attention  # noqa: F401  (registers)
+
+    return {"attn_implementation": attn_implementation}
+
+
 @ginlite.configurable(name="LCRec")
 class LCRec(nn.Module):
     def __init__(self, pretrained_path: Optional[str] = None,
-                 config=None) -> None:
+                 config=None,
+                 attn_implementation: Optional[str] = None) -> None:
         super().__init__()
         from transformers import AutoModelForCausalLM, AutoTokenizer
 
+        self.attn_implementation = attn_implementation
+        attn_kw = _attn_kwargs(attn_implementation)
         if pretrained_path and os.path.isdir(pretrained_path):
             self.tokenizer = AutoTokenizer.from_pretrained(pretrained_path)
-            self.model = AutoModelForCausalLM.from_pretrained(pretrained_path)
+            self.model = AutoModelForCausalLM.from_pretrained(
+                pretrained_path, **attn_kw)
         else:
             from genrec_amd.utils.tokenizer import build_offline_tokenizer
 
@@ -67,7 +82,7 @@ class LCRec(nn.Module):
                 vocab_size=max(len(self.tokenizer), 512))
             if cfg.vocab_size < len(self.tokenizer):
                 cfg.vocab_size = len(self.tokenizer)
-            self.model = AutoModelForCausalLM.from_config(cfg)
+            self.model = AutoModelForCausalLM.from_config(cfg, **attn_kw)
 
     def gradient_checkpointing_enable(self):
         self.model.gradient_checkpointing_enable()
@@ -118,7 +133,8 @@ class LCRec(nn.Module):
 
         self.tokenizer = AutoTokenizer.from_pretrained(load_dir)
         self.model = AutoModelForCausalLM.from_pretrained(
-            load_dir, torch_dtype=torch.bfloat16)
+            load_dir, torch_dtype=torch.bfloat16,
+            **_attn_kwargs(self.attn_implementation))
         logger.info("Loaded checkpoint from %s", load_dir)
 
     @torch.no_grad()

@@ -54,8 +54,14 @@ class Query2Embedding(nn.Module):
                  item_token: str = "[EMB]", pad_token: str = "<|pad|>",
                  eos_token: str = "<|endoftext|>",
                  gradient_checkpointing: bool = True, tau: float = 3.0,
-                 alpha: float = 0.01, hardneg_r: float = 0.1) -> None:
+                 alpha: float = 0.01, hardneg_r: float = 0.1,
+                 attn_implementation: Optional[str] = None) -> None:
         super().__init__()
+        # None keeps the transformers default; "genrec_gqa" routes the
+        # Qwen2 layers through the project's grouped-query flash kernel
+        from genrec_amd.models.lcrec import _attn_kwargs
+
+        attn_kw = _attn_kwargs(attn_implementation)
         self.tau = nn.Parameter(torch.tensor(tau))
         self.alpha, self.hardneg_r = alpha, hardneg_r
         self.item_token = item_token
@@ -64,7 +70,8 @@ class Query2Embedding(nn.Module):
 
             self.tokenizer = AutoTokenizer.from_pretrained(
                 pretrained_path, pad_token=pad_token, eos_token=eos_token)
-            self.model = AutoModelForCausalLM.from_pretrained(pretrained_path)
+            self.model = AutoModelForCausalLM.from_pretrained(
+                pretrained_path, **attn_kw)
         else:
             from transformers import AutoModelForCausalLM
 
@@ -74,7 +81,7 @@ class Query2Embedding(nn.Module):
             self.tokenizer = build_offline_tokenizer(eos_token=eos_token)
             cfg = config or default_qwen_config(
                 vocab_size=max(len(self.tokenizer) + 8, 512))
-            self.model = AutoModelForCausalLM.from_config(cfg)
+            self.model = AutoModelForCausalLM.from_config(cfg, **attn_kw)
         if freeze_lm:
             for p in self.model.parameters():
                 p.requires_grad = False

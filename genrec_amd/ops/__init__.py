@@ -84,6 +84,7 @@ from genrec_amd.ops.attention import (  # noqa: E402
     t5_attention,
     hstu_pointwise_attention,
     hstu_fused_attention,
+    gqa_flash_attention,
 )
 from genrec_amd.ops.quantize import residual_quantize_step  # noqa: E402
 from genrec_amd.ops.losses import softmax_ce, tied_softmax_ce, summed_ce  # noqa: E402
@@ -105,6 +106,7 @@ __all__ = [
     "t5_attention",
     "hstu_pointwise_attention",
     "hstu_fused_attention",
+    "gqa_flash_attention",
     "residual_quantize_step",
     "softmax_ce",
     "tied_softmax_ce",

@@ -389,3 +389,79 @@ def hstu_fused_attention(q, k, v, pos_bucket, pos_weight, time_weight,
         return _HstuAttnFn.apply(q, k, v, pos_weight, time_weight,
                                  pos_bucket.contiguous(), ts, kp)
     return None  # caller composes the bias-tensor path
+
+
+class _GqaFlashAttnFn(torch.autograd.Function):
+    """Grouped-query flash attention (csrc/kernels/attention_gqa.hip):
+    forward saves only out + lse; backward recomputes S per tile in two
+    atomic-free kernels (bitwise run-to-run deterministic)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, key_pad_mask, scale, causal):
+        from genrec_amd import ops
+
+        out, lse = ops.ext().gqa_attn_fwd(q, k, v, key_pad_mask, scale,
+                                          causal)
+        ctx.save_for_backward(
+            q, k, v, out, lse,
+            key_pad_mask if key_pad_mask is not None else torch.empty(0))
+        ctx.meta = (scale, causal)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from genrec_amd import ops
+
+        q, k, v, out, lse, key_pad_mask = ctx.saved_tensors
+        scale, causal = ctx.meta
+        # dq/dk/dv come back as [B,H,L,D] views of [B,L,H,D] storage
+        dq, dk, dv = ops.ext().gqa_attn_bwd(
+            dout, q, k, v, out, lse,
+            key_pad_mask if key_pad_mask.numel() else None, scale, causal)
+        return dq, dk, dv, None, None, None
+
+
+GQA_HEAD_DIMS = (64, 128)
+
+
+def gqa_kernel_supported(q: Tensor, k: Tensor, v: Tensor) -> bool:
+    """True iff gqa_flash_attention would run the HIP kernel on these
+    inputs (GPU, bf16, D in {64,128}, Hq % Hkv == 0, not disabled)."""
+    if os.environ.get("GENREC_DISABLE_ATTN_GQA", "0") == "1":
+        return False
+    if not (q.dim() == 4 and k.dim() == 4 and v.dim() == 4):
+        return False
+    if not (q.dtype == k.dtype == v.dtype == torch.bfloat16):
+        return False
+    if q.size(3) not in GQA_HEAD_DIMS or k.size(3) != q.size(3) \
+            or v.shape != k.shape or k.size(0) != q.size(0):
+        return False
+    if k.size(1) == 0 or q.size(1) % k.size(1) != 0:
+        return False
+    if q.size(0) == 0 or q.size(2) == 0 or k.size(2) == 0:
+        return False
+    return _kernel_available("gqa_attn_fwd", q, k, v)
+
+
+def gqa_flash_attention(
+    q: Tensor,  # [B, Hq, Lq, D]
+    k: Tensor,  # [B, Hkv, Lk, D]
+    v: Tensor,  # [B, Hkv, Lk, D]
+    *,
+    key_pad_mask: Optional[Tensor] = None,  # [B, Lk] bool, True = PAD
+    scale: float,
+    causal: bool = True,
+) -> Tensor:
+    """Grouped-query causal attention for LLM backbones -> [B, Lq, Hq, D].
+
+    Query head h reads KV head h // (Hq // Hkv); query row i sits at
+    absolute position Lk - Lq + i. Exact (-inf) masking; rows with no
+    visible key return 0. q/k/v may be [B,L,H,D] transpose views.
+    """
+    if gqa_kernel_supported(q, k, v):
+        kp = None
+        if key_pad_mask is not None:
+            kp = key_pad_mask.to(torch.bool).contiguous()
+        return _GqaFlashAttnFn.apply(q, k, v, kp, float(scale), bool(causal))
+    return eager.gqa_attention(q, k, v, key_pad_mask=key_pad_mask,
+                               scale=scale, causal=causal)

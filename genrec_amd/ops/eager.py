@@ -91,6 +91,49 @@ def fused_attention(
     return torch.matmul(attn, v)
 
 
+def gqa_attention(
+    q: Tensor,  # [B, Hq, Lq, D]
+    k: Tensor,  # [B, Hkv, Lk, D]
+    v: Tensor,  # [B, Hkv, Lk, D]
+    *,
+    key_pad_mask: Optional[Tensor] = None,  # [B, Lk] bool, True = PAD
+    scale: float,
+    causal: bool = True,
+) -> Tensor:
+    """Grouped-query softmax attention, fp32 math -> [B, Lq, Hq, D].
+
+    Query head h reads KV head h // (Hq // Hkv) (no K/V expansion). Query
+    row i sits at absolute position Lk - Lq + i and, when causal, sees keys
+    j <= Lk - Lq + i (prefill, cached decode and chunked decode). Masking
+    is exact (-inf); a row with no visible key returns 0 and has zero
+    gradients.
+    """
+    B, Hq, Lq, D = q.shape
+    Hkv, Lk = k.size(1), k.size(2)
+    if Hq % Hkv != 0:
+        raise ValueError(f"Hq={Hq} is not a multiple of Hkv={Hkv}")
+    g = Hq // Hkv
+    qf = q.float().reshape(B, Hkv, g, Lq, D)
+    kf, vf = k.float(), v.float()
+    scores = torch.einsum("bkgqd,bkld->bkgql", qf, kf) * scale
+    visible = torch.ones(B, 1, 1, Lq, Lk, dtype=torch.bool, device=q.device)
+    if causal:
+        i = torch.arange(Lq, device=q.device)[:, None] + (Lk - Lq)
+        j = torch.arange(Lk, device=q.device)[None, :]
+        visible = visible & (j <= i)
+    if key_pad_mask is not None:
+        visible = visible & ~key_pad_mask.bool()[:, None, None, None, :]
+    any_visible = visible.any(dim=-1, keepdim=True)
+    scores = scores.masked_fill(~visible, float("-inf"))
+    # rows with no visible key: softmax over zeros, then zeroed (no NaN)
+    scores = torch.where(any_visible, scores, torch.zeros_like(scores))
+    probs = torch.softmax(scores, dim=-1)
+    probs = torch.where(any_visible, probs, torch.zeros_like(probs))
+    out = torch.einsum("bkgql,bkld->bkgqd", probs, vf)
+    out = out.reshape(B, Hq, Lq, D).transpose(1, 2).contiguous()
+    return out.to(q.dtype)
+
+
 def pairwise_sqdist(x: Tensor, codebook: Tensor) -> Tensor:
     """L2 distance matrix ||x||^2 + ||c||^2 - 2 x c^T (ref rqvae.py:186-192)."""
     return (

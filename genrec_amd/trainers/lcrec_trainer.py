@@ -241,6 +241,8 @@ def train(
     amp: bool = True,                          # False -> fp32 eval/train
     debug_logging: bool = False,               # print target-vs-pred samples
     max_text_len: Optional[int] = None,        # forwarded to the dataset
+    # None = transformers default; "genrec_gqa" = project GQA flash kernel
+    attn_implementation: Optional[str] = None,
 ):
     if max_length is not None:
         max_seq_len = max_length
@@ -254,11 +256,13 @@ def train(
     common.set_seed(seed, ctx.rank)
     device = ctx.device
 
-    model = LCRec(pretrained_path=pretrained_path)
+    model = LCRec(pretrained_path=pretrained_path,
+                  attn_implementation=attn_implementation)
     if backbone_config is not None:
         from genrec_amd.models.lcrec import default_qwen_config
 
-        model = LCRec(config=default_qwen_config(**backbone_config))
+        model = LCRec(config=default_qwen_config(**backbone_config),
+                      attn_implementation=attn_implementation)
     model.add_codebook_tokens(n_codebooks, codebook_size)
     if checkpoint_path and os.path.isdir(checkpoint_path):
         model.load_pretrained(checkpoint_path)

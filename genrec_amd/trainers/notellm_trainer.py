@@ -79,6 +79,8 @@ def train(
     max_steps: Optional[int] = None,
     num_workers: int = 0,
     eval_max_batches: Optional[int] = None,
+    # None = transformers default; "genrec_gqa" = project GQA flash kernel
+    attn_implementation: Optional[str] = None,
 ):
     common.enable_tuned_gemms()
     ctx = init_distributed()
@@ -92,7 +94,8 @@ def train(
 
         cfg = default_qwen_config(**backbone_config)
     model = Query2Embedding(pretrained_path=pretrained_path, config=cfg,
-                            gradient_checkpointing=gradient_checkpointing
+                            gradient_checkpointing=gradient_checkpointing,
+                            attn_implementation=attn_implementation
                             ).to(device)
     broadcast_parameters(model)
     opt = torch.optim.AdamW(model.parameters(), lr=learning_rate,

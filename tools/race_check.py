@@ -106,6 +106,28 @@ def build_cases():
         return ops.ext().attn_bwd_flash(doutf, qf, kf, vf, fo, fs, fml, fdm,
                                         None, 0.125, 0.0, False, 0)[:3]
 
+    # grouped-query flash attention: 6 query heads on 1 KV head, D=128,
+    # three tiles with a ragged tail, left padding; [B,L,H,D] views in
+    Lg, Dg = 130, 128
+    qg = torch.randn(B, Lg, 6, Dg, device=dev,
+                     dtype=torch.bfloat16).transpose(1, 2)
+    kg = torch.randn(B, Lg, 1, Dg, device=dev,
+                     dtype=torch.bfloat16).transpose(1, 2)
+    vg = torch.randn_like(kg)
+    doutg = torch.randn(B, Lg, 6, Dg, device=dev, dtype=torch.bfloat16)
+    padg = torch.arange(Lg, device=dev)[None, :] < torch.tensor(
+        [70, 0, 3, 0], device=dev)[:, None]
+    sg = Dg ** -0.5
+
+    def gqa_fwd():
+        return ops.ext().gqa_attn_fwd(qg, kg, vg, padg, sg, True)
+
+    go, glse = ops.ext().gqa_attn_fwd(qg, kg, vg, padg, sg, True)
+
+    def gqa_bwd():
+        return ops.ext().gqa_attn_bwd(doutg, qg, kg, vg, go, glse, padg,
+                                      sg, True)
+
     x = torch.randn(4096, 384, device=dev, dtype=torch.bfloat16)
     w = torch.randn(384, device=dev, dtype=torch.bfloat16)
 
@@ -139,6 +161,9 @@ def build_cases():
         # flash bwd accumulates dQ with fp32 global atomics -> order-
         # dependent rounding; tolerance instead of bitwise
         ("attn_bwd_flash", flash_bwd, 2e-3),
+        # no atomics anywhere: bitwise
+        ("gqa_attn_fwd", gqa_fwd, 0.0),
+        ("gqa_attn_bwd", gqa_bwd, 0.0),
         ("rms_norm", rms, 0.0),
         ("layer_norm_fwd", ln_fwd, 0.0),
         ("layer_norm_bwd", ln_bwd, 0.0),
