@@ -84,6 +84,13 @@ std::vector<torch::Tensor> layer_norm_bwd(torch::Tensor dy, torch::Tensor x,
                                           torch::Tensor rstd);
 torch::Tensor dropout_fuse_bwd(torch::Tensor dy, torch::Tensor mask,
                                double p, bool relu);
+std::vector<torch::Tensor> dropout_add_rms_norm_fwd(
+    torch::Tensor y, torch::Tensor residual, torch::Tensor w, double p,
+    double eps, bool t5_style, int64_t seed,
+    c10::optional<torch::Tensor> seed_dev);
+std::vector<torch::Tensor> dropout_add_rms_norm_bwd(
+    torch::Tensor dn, c10::optional<torch::Tensor> dh, torch::Tensor h,
+    torch::Tensor w, torch::Tensor inv_rms, torch::Tensor mask, double p);
 torch::Tensor topk_hit_ranks(torch::Tensor actual, torch::Tensor topk);
 void fused_adamw(torch::Tensor master, torch::Tensor grad, torch::Tensor m,
                  torch::Tensor v, torch::Tensor out_p, torch::Tensor lr,
@@ -154,6 +161,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layer_norm_fwd", &genrec::layer_norm_fwd, "fused LayerNorm fwd");
   m.def("layer_norm_bwd", &genrec::layer_norm_bwd, "fused LayerNorm bwd");
   m.def("dropout_fuse_bwd", &genrec::dropout_fuse_bwd, "fused dropout bwd");
+  m.def("dropout_add_rms_norm_fwd", &genrec::dropout_add_rms_norm_fwd,
+        "fused residual+dropout -> RMSNorm fwd -> (h, n, mask, inv_rms)");
+  m.def("dropout_add_rms_norm_bwd", &genrec::dropout_add_rms_norm_bwd,
+        "fused RMSNorm bwd + dh add + dropout bwd -> (t, dy, dw)");
   m.def("topk_hit_ranks", &genrec::topk_hit_ranks, "first-match ranks");
   m.def("fused_adamw", &genrec::fused_adamw,
         "fused flat AdamW step (device lr/scale/step scalars)");

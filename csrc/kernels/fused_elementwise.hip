@@ -4,6 +4,8 @@
 // elementwise kernels per TIGER step; each is ~4-8 us of pure launch+
 // stream time inside the captured graph. Fusing halves the count and the
 // bytes moved. Masks are saved as bytes for exact backward replay.
+// (A residual+dropout that feeds an RMSNorm runs fused with that norm:
+// dropout_add_rms_norm_* in norms.hip, same RNG stream and mask bytes.)
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>

@@ -8,6 +8,10 @@
 // (normalize.py:38-55, 73-95). Backward reduces dweight per-block in LDS
 // into one partial row per block, finished by a fixed-order two-stage
 // column reduce (deterministic, no atomics).
+//
+// Pre-norm transformer blocks pair every RMSNorm but the first with the
+// residual+dropout in front of it: dropout_add_rms_norm_{fwd,bwd} run that
+// pair as one pass each way, bit-identical to the separate kernels.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -254,6 +258,181 @@ __global__ void rms_norm_bwd_v2_kernel(const unsigned int* __restrict__ dy,
   for (int j = lane; j < d2; j += WAVE, ci += 2) {
     dw_lds[wave_in_block * d + 2 * j] = dw_acc[ci];
     dw_lds[wave_in_block * d + 2 * j + 1] = dw_acc[ci + 1];
+  }
+  __syncthreads();
+  for (int j = (int)threadIdx.x; j < d; j += (int)blockDim.x) {
+    float s = dw_lds[j] + dw_lds[d + j] + dw_lds[2 * d + j] +
+              dw_lds[3 * d + j];
+    dw[(int64_t)blockIdx.x * d + j] = s;
+  }
+}
+
+// ------------------------------------------- dropout-add + RMSNorm (fused)
+// Pre-norm blocks compute h = residual + dropout(y) and then n = norm(h).
+// Run as two kernels the second re-reads the h the first just wrote, and
+// the backward needs three passes (norm bwd, autograd's dh + g add,
+// dropout bwd). These two kernels do each direction in one pass with the
+// row held in registers. bf16 rows and bf16 weight only, so the T5 and
+// standard styles share one rounding sequence: bf16(x * r), times w.
+//
+// Forward is bit-identical to dropout_fuse_fwd_v4 followed by
+// rms_norm_fwd_v2: same RNG stream (hash_rng(s, row*d + col)), same mask
+// bytes, h rounded to bf16 BEFORE the sum of squares, and the same
+// lane -> column-pair mapping so the fp32 sums associate identically.
+// Backward is bit-identical to rms_norm_bwd_v2 + bf16 add + dropout bwd:
+// g is rounded to bf16 before dh is added (what autograd's add sees), and
+// the dw partials use rms_norm_bwd's block/wave -> row mapping.
+//
+// NDW = column-pair dwords per lane held in registers (d <= 128 * NDW).
+
+template <int NDW>
+__global__ void __launch_bounds__(256) dropout_add_rms_norm_fwd_kernel(
+    const unsigned int* __restrict__ y, const unsigned int* __restrict__ res,
+    const __hip_bfloat16* __restrict__ w, unsigned int* __restrict__ h,
+    unsigned int* __restrict__ n, unsigned short* __restrict__ mask,
+    float* __restrict__ inv_rms, int64_t n_rows, int d2, float eps, float p,
+    float inv_keep, unsigned int seed,
+    const unsigned int* __restrict__ seed_dev) {
+  const int wave_id = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int n_waves = gridDim.x * blockDim.x / WAVE;
+  const int d = d2 * 2;
+  const unsigned int s = seed + (seed_dev ? *seed_dev : 0u);
+  const unsigned int thresh = (unsigned int)(p * 16777216.0f);
+  for (int64_t row = wave_id; row < n_rows; row += n_waves) {
+    const int64_t rbase = row * d2;
+    BF16x2 yv[NDW], rv[NDW], hv[NDW];
+#pragma unroll
+    for (int c = 0; c < NDW; ++c) {
+      const int j = lane + c * WAVE;
+      yv[c].u = j < d2 ? y[rbase + j] : 0u;
+      rv[c].u = j < d2 ? res[rbase + j] : 0u;
+    }
+    float ss = 0.f;
+#pragma unroll
+    for (int c = 0; c < NDW; ++c) {
+      const int j = lane + c * WAVE;
+      if (j < d2) {
+        const int64_t base = (rbase + j) * 2;
+        unsigned int mm = 0;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          float v = to_f32(yv[c].e[k]);
+          bool keep = (hash_rng(s, base + k) & 0xFFFFFF) >= thresh;
+          mm |= (keep ? 1u : 0u) << (8 * k);
+          v = keep ? v * inv_keep : 0.f;
+          v += to_f32(rv[c].e[k]);
+          hv[c].e[k] = from_f32<__hip_bfloat16>(v);
+        }
+        h[rbase + j] = hv[c].u;
+        mask[rbase + j] = (unsigned short)mm;
+        float a = to_f32(hv[c].e[0]), b = to_f32(hv[c].e[1]);
+        ss += a * a + b * b;
+      }
+    }
+    ss = wave_sum(ss);
+    float r = rsqrtf(ss / d + eps);
+    if (lane == 0) inv_rms[row] = r;
+#pragma unroll
+    for (int c = 0; c < NDW; ++c) {
+      const int j = lane + c * WAVE;
+      if (j < d2) {
+        BF16x2 o;
+        float wf[2];
+        load_w2(w, j, wf);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          float t = to_f32(hv[c].e[k]) * r;
+          t = to_f32(from_f32<__hip_bfloat16>(t));
+          o.e[k] = from_f32<__hip_bfloat16>(wf[k] * t);
+        }
+        n[rbase + j] = o.u;
+      }
+    }
+  }
+}
+
+template <int NDW, bool HAS_DH>
+__global__ void __launch_bounds__(256) dropout_add_rms_norm_bwd_kernel(
+    const unsigned int* __restrict__ dn, const unsigned int* __restrict__ dh,
+    const unsigned int* __restrict__ h, const __hip_bfloat16* __restrict__ w,
+    const float* __restrict__ inv_rms, const unsigned short* __restrict__ mask,
+    unsigned int* __restrict__ t, unsigned int* __restrict__ dy,
+    float* __restrict__ dw, int64_t n_rows, int d2, float inv_keep) {
+  const int wave_in_block = threadIdx.x / WAVE;
+  const int waves_per_block = blockDim.x / WAVE;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int64_t wave_id = (int64_t)blockIdx.x * waves_per_block + wave_in_block;
+  const int64_t n_waves = (int64_t)gridDim.x * waves_per_block;
+  const int d = d2 * 2;
+
+  float dw_acc[2 * NDW];
+  float wf[2 * NDW];
+#pragma unroll
+  for (int c = 0; c < NDW; ++c) {
+    const int j = lane + c * WAVE;
+    dw_acc[2 * c] = dw_acc[2 * c + 1] = 0.f;
+    wf[2 * c] = wf[2 * c + 1] = 0.f;
+    if (j < d2) load_w2(w, j, wf + 2 * c);
+  }
+
+  for (int64_t row = wave_id; row < n_rows; row += n_waves) {
+    const int64_t rbase = row * d2;
+    BF16x2 xv[NDW], gv[NDW], hv[NDW];
+    unsigned int mm[NDW];
+#pragma unroll
+    for (int c = 0; c < NDW; ++c) {
+      const int j = lane + c * WAVE;
+      xv[c].u = j < d2 ? h[rbase + j] : 0u;
+      gv[c].u = j < d2 ? dn[rbase + j] : 0u;
+      if (HAS_DH) hv[c].u = j < d2 ? dh[rbase + j] : 0u;
+      mm[c] = j < d2 ? (unsigned int)mask[rbase + j] : 0u;
+    }
+    float r = inv_rms[row];
+    float dot = 0.f;
+#pragma unroll
+    for (int c = 0; c < NDW; ++c) {
+      const int j = lane + c * WAVE;
+      if (j < d2) {
+        dot += wf[2 * c] * to_f32(gv[c].e[0]) * to_f32(xv[c].e[0]) +
+               wf[2 * c + 1] * to_f32(gv[c].e[1]) * to_f32(xv[c].e[1]);
+      }
+    }
+    dot = wave_sum(dot);
+    float coef = r * r * r / d * dot;
+#pragma unroll
+    for (int c = 0; c < NDW; ++c) {
+      const int j = lane + c * WAVE;
+      if (j < d2) {
+        BF16x2 to, yo;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          float xf = to_f32(xv[c].e[k]);
+          float dyf = to_f32(gv[c].e[k]);
+          __hip_bfloat16 g =
+              from_f32<__hip_bfloat16>(wf[2 * c + k] * dyf * r - coef * xf);
+          dw_acc[2 * c + k] += dyf * xf * r;
+          if (HAS_DH)
+            g = from_f32<__hip_bfloat16>(to_f32(hv[c].e[k]) + to_f32(g));
+          bool keep = (mm[c] >> (8 * k)) & 1u;
+          to.e[k] = g;
+          yo.e[k] =
+              from_f32<__hip_bfloat16>(keep ? to_f32(g) * inv_keep : 0.f);
+        }
+        t[rbase + j] = to.u;
+        dy[rbase + j] = yo.u;
+      }
+    }
+  }
+  // same per-block dw partial row as rms_norm_bwd_v2_kernel
+  extern __shared__ __attribute__((aligned(16))) float dw_lds[];  // [4][d]
+#pragma unroll
+  for (int c = 0; c < NDW; ++c) {
+    const int j = lane + c * WAVE;
+    if (j < d2) {
+      dw_lds[wave_in_block * d + 2 * j] = dw_acc[2 * c];
+      dw_lds[wave_in_block * d + 2 * j + 1] = dw_acc[2 * c + 1];
+    }
   }
   __syncthreads();
   for (int j = (int)threadIdx.x; j < d; j += (int)blockDim.x) {
@@ -817,6 +996,48 @@ __global__ void rms_dw_reduce2_kernel(const float* __restrict__ tmp,
   if (lane == 0) out[j] = from_f32<WT>(acc);
 }
 
+// Block cap of the RMSNorm backward kernels: 1024 blocks = 4096 waves
+// (4 blocks/CU) hide the per-row wave_sum serialization at the big
+// [15616, 384] shapes — same-box A/B vs the old 512 cap: 48.3k -> 49.5k
+// samples/s on the TIGER bench (2048 flat vs 1024). The dw partial matrix
+// grows with the cap but the adaptive two-stage reduce absorbs it.
+// GENREC_RMS_BWD_CAP overrides for A/B.
+static int rms_bwd_block_cap() {
+  static const int cap = [] {
+    const char* e = getenv("GENREC_RMS_BWD_CAP");
+    int v = e ? atoi(e) : 1024;
+    return (v >= 64 && v <= 4096) ? v : 1024;
+  }();
+  return cap;
+}
+
+// dw = column sum of the [n_blocks, d] fp32 partials, cast to w's dtype
+static torch::Tensor rms_dw_finish(const torch::Tensor& dw, int n_blocks,
+                                   int d, const torch::Tensor& w,
+                                   hipStream_t stream) {
+  auto dw_out = torch::empty({(int64_t)d}, w.options());
+  int ch = 32;
+  while ((int64_t)ch * d < 131072 && ch < 512 && ch * 4 < n_blocks) ch *= 2;
+  auto dw_tmp = torch::empty({ch, (int64_t)d}, dw.options());
+  dim3 rblock(256);
+  dim3 rgrid1((unsigned)(((int64_t)ch * d + 255) / 256));
+  hipLaunchKernelGGL(rms_dw_reduce1_kernel, rgrid1, rblock, 0, stream,
+                     dw.data_ptr<float>(), dw_tmp.data_ptr<float>(),
+                     n_blocks, d, ch);
+  dim3 rgrid2((unsigned)((d + 3) / 4));  // 4 waves/block, one wave per col
+  if (w.scalar_type() == torch::kBFloat16) {
+    hipLaunchKernelGGL((rms_dw_reduce2_kernel<__hip_bfloat16>), rgrid2,
+                       rblock, 0, stream, dw_tmp.data_ptr<float>(),
+                       reinterpret_cast<__hip_bfloat16*>(dw_out.data_ptr()),
+                       d, ch);
+  } else {
+    hipLaunchKernelGGL((rms_dw_reduce2_kernel<float>), rgrid2, rblock, 0,
+                       stream, dw_tmp.data_ptr<float>(),
+                       dw_out.data_ptr<float>(), d, ch);
+  }
+  return dw_out;
+}
+
 std::vector<torch::Tensor> rms_norm_bwd(torch::Tensor dy, torch::Tensor x,
                                         torch::Tensor w, torch::Tensor inv_rms,
                                         bool t5_style) {
@@ -828,18 +1049,7 @@ std::vector<torch::Tensor> rms_norm_bwd(torch::Tensor dy, torch::Tensor x,
   bool w_bf16 = w.scalar_type() == torch::kBFloat16;
   auto dx = torch::empty_like(x);
   dim3 block(256);
-  // Block cap: 1024 blocks = 4096 waves (4 blocks/CU) hide the per-row
-  // wave_sum serialization at the big [15616, 384] shapes — same-box A/B
-  // vs the old 512 cap: 48.3k -> 49.5k samples/s on the TIGER bench
-  // (2048 flat vs 1024). The dw partial matrix grows with the cap but
-  // the adaptive two-stage reduce absorbs it. GENREC_RMS_BWD_CAP
-  // overrides for A/B.
-  static const int cap = [] {
-    const char* e = getenv("GENREC_RMS_BWD_CAP");
-    int v = e ? atoi(e) : 1024;
-    return (v >= 64 && v <= 4096) ? v : 1024;
-  }();
-  int n_blocks = std::min(grid_for_rows(n_rows, 4), cap);
+  int n_blocks = std::min(grid_for_rows(n_rows, 4), rms_bwd_block_cap());
   dim3 grid(n_blocks);
   auto dw = torch::empty({n_blocks, (int64_t)d},
                          x.options().dtype(torch::kFloat32));
@@ -895,28 +1105,135 @@ std::vector<torch::Tensor> rms_norm_bwd(torch::Tensor dy, torch::Tensor x,
   }
 #undef LAUNCH_RMSB_W
 #undef LAUNCH_RMSB
-  auto dw_out = torch::empty({(int64_t)d}, w.options());
-  int ch = 32;
-  while ((int64_t)ch * d < 131072 && ch < 512 && ch * 4 < n_blocks) ch *= 2;
-  auto dw_tmp = torch::empty({ch, (int64_t)d},
-                             x.options().dtype(torch::kFloat32));
-  dim3 rblock(256);
-  dim3 rgrid1((unsigned)(((int64_t)ch * d + 255) / 256));
-  hipLaunchKernelGGL(rms_dw_reduce1_kernel, rgrid1, rblock, 0, stream,
-                     dw.data_ptr<float>(), dw_tmp.data_ptr<float>(),
-                     n_blocks, d, ch);
-  dim3 rgrid2((unsigned)((d + 3) / 4));  // 4 waves/block, one wave per col
-  if (w_bf16) {
-    hipLaunchKernelGGL((rms_dw_reduce2_kernel<__hip_bfloat16>), rgrid2,
-                       rblock, 0, stream, dw_tmp.data_ptr<float>(),
-                       reinterpret_cast<__hip_bfloat16*>(dw_out.data_ptr()),
-                       d, ch);
-  } else {
-    hipLaunchKernelGGL((rms_dw_reduce2_kernel<float>), rgrid2, rblock, 0,
-                       stream, dw_tmp.data_ptr<float>(),
-                       dw_out.data_ptr<float>(), d, ch);
+  return {dx, rms_dw_finish(dw, n_blocks, d, w, stream)};
+}
+
+// ---- fused dropout-add + RMSNorm (kernels above; op in ops/fused.py)
+
+static int addnorm_ndw(int d) {
+  const int per_lane = (d / 2 + WAVE - 1) / WAVE;
+  return per_lane <= 2 ? 2 : (per_lane <= 4 ? 4 : 8);
+}
+
+std::vector<torch::Tensor> dropout_add_rms_norm_fwd(
+    torch::Tensor y, torch::Tensor residual, torch::Tensor w, double p,
+    double eps, bool t5_style, int64_t seed,
+    c10::optional<torch::Tensor> seed_dev) {
+  (void)t5_style;  // one rounding sequence for a bf16 weight (kernel comment)
+  TORCH_CHECK(y.is_cuda() && y.is_contiguous() && residual.is_cuda() &&
+              residual.is_contiguous() && w.is_cuda());
+  TORCH_CHECK(y.scalar_type() == torch::kBFloat16 &&
+              residual.scalar_type() == torch::kBFloat16 &&
+              w.scalar_type() == torch::kBFloat16,
+              "dropout_add_rms_norm: bf16 only");
+  TORCH_CHECK(y.dim() >= 1 && y.sizes() == residual.sizes(),
+              "dropout_add_rms_norm: shape mismatch");
+  const int d = y.size(-1);
+  TORCH_CHECK(d > 0 && (d & 1) == 0 && d <= WAVE * RMS_MAX_COLS_PER_LANE &&
+              w.numel() == d, "dropout_add_rms_norm: unsupported d");
+  const int64_t n_rows = y.numel() / d;
+  auto wc = w.contiguous();
+  auto h = torch::empty_like(y);
+  auto n = torch::empty_like(y);
+  auto mask = torch::empty({y.numel()}, y.options().dtype(torch::kUInt8));
+  auto inv_rms = torch::empty({n_rows}, y.options().dtype(torch::kFloat32));
+  TORCH_CHECK(ptr_aligned4(y.data_ptr()) && ptr_aligned4(residual.data_ptr()) &&
+              ptr_aligned4(wc.data_ptr()) && ptr_aligned4(h.data_ptr()) &&
+              ptr_aligned4(n.data_ptr()) && ptr_aligned4(mask.data_ptr()),
+              "dropout_add_rms_norm: unaligned pointer");
+  if (n_rows == 0) return {h, n, mask, inv_rms};
+  float inv_keep = p < 1.0 ? 1.0f / (1.0f - (float)p) : 0.f;
+  dim3 block(256);
+  dim3 grid(grid_for_rows(n_rows, 4));
+  auto stream = at::cuda::getCurrentHIPStream();
+#define LAUNCH_ADDNORM_F(NDW)                                                  \
+  hipLaunchKernelGGL((dropout_add_rms_norm_fwd_kernel<NDW>), grid, block, 0,   \
+      stream, reinterpret_cast<const unsigned int*>(y.data_ptr()),             \
+      reinterpret_cast<const unsigned int*>(residual.data_ptr()),              \
+      reinterpret_cast<const __hip_bfloat16*>(wc.data_ptr()),                  \
+      reinterpret_cast<unsigned int*>(h.data_ptr()),                           \
+      reinterpret_cast<unsigned int*>(n.data_ptr()),                           \
+      reinterpret_cast<unsigned short*>(mask.data_ptr<unsigned char>()),       \
+      inv_rms.data_ptr<float>(), n_rows, d / 2, (float)eps, (float)p,          \
+      inv_keep, (unsigned int)seed,                                            \
+      seed_dev.has_value()                                                     \
+          ? reinterpret_cast<const unsigned int*>(seed_dev->data_ptr())        \
+          : nullptr)
+  switch (addnorm_ndw(d)) {
+    case 2: LAUNCH_ADDNORM_F(2); break;
+    case 4: LAUNCH_ADDNORM_F(4); break;
+    default: LAUNCH_ADDNORM_F(8); break;
   }
-  return {dx, dw_out};
+#undef LAUNCH_ADDNORM_F
+  return {h, n, mask, inv_rms};
+}
+
+std::vector<torch::Tensor> dropout_add_rms_norm_bwd(
+    torch::Tensor dn, c10::optional<torch::Tensor> dh, torch::Tensor h,
+    torch::Tensor w, torch::Tensor inv_rms, torch::Tensor mask, double p) {
+  const bool has_dh = dh.has_value();
+  TORCH_CHECK(dn.is_cuda() && dn.is_contiguous() && h.is_contiguous() &&
+              mask.is_contiguous() && inv_rms.is_contiguous() &&
+              (!has_dh || dh->is_contiguous()));
+  TORCH_CHECK(dn.scalar_type() == torch::kBFloat16 &&
+              h.scalar_type() == torch::kBFloat16 &&
+              w.scalar_type() == torch::kBFloat16 &&
+              (!has_dh || dh->scalar_type() == torch::kBFloat16) &&
+              mask.scalar_type() == torch::kUInt8 &&
+              inv_rms.scalar_type() == torch::kFloat32,
+              "dropout_add_rms_norm_bwd: dtype mismatch");
+  const int d = h.size(-1);
+  TORCH_CHECK(d > 0 && (d & 1) == 0 && d <= WAVE * RMS_MAX_COLS_PER_LANE &&
+              w.numel() == d, "dropout_add_rms_norm_bwd: unsupported d");
+  const int64_t n_rows = h.numel() / d;
+  TORCH_CHECK(dn.numel() == h.numel() && mask.numel() == h.numel() &&
+              inv_rms.numel() == n_rows &&
+              (!has_dh || dh->numel() == h.numel()),
+              "dropout_add_rms_norm_bwd: shape mismatch");
+  auto wc = w.contiguous();
+  auto t = torch::empty_like(h);
+  auto dy = torch::empty_like(h);
+  TORCH_CHECK(ptr_aligned4(dn.data_ptr()) && ptr_aligned4(h.data_ptr()) &&
+              ptr_aligned4(wc.data_ptr()) && ptr_aligned4(mask.data_ptr()) &&
+              ptr_aligned4(t.data_ptr()) && ptr_aligned4(dy.data_ptr()) &&
+              (!has_dh || ptr_aligned4(dh->data_ptr())),
+              "dropout_add_rms_norm_bwd: unaligned pointer");
+  if (n_rows == 0) return {t, dy, torch::zeros({(int64_t)d}, w.options())};
+  float inv_keep = p < 1.0 ? 1.0f / (1.0f - (float)p) : 0.f;
+  dim3 block(256);
+  // same grid as rms_norm_bwd, so the dw partials are the same numbers
+  int n_blocks = std::min(grid_for_rows(n_rows, 4), rms_bwd_block_cap());
+  dim3 grid(n_blocks);
+  auto dw = torch::empty({n_blocks, (int64_t)d},
+                         h.options().dtype(torch::kFloat32));
+  size_t smem = 4 * (size_t)d * sizeof(float);
+  auto stream = at::cuda::getCurrentHIPStream();
+#define LAUNCH_ADDNORM_B(NDW, HAS_DH)                                          \
+  hipLaunchKernelGGL((dropout_add_rms_norm_bwd_kernel<NDW, HAS_DH>), grid,     \
+      block, smem, stream,                                                     \
+      reinterpret_cast<const unsigned int*>(dn.data_ptr()),                    \
+      HAS_DH ? reinterpret_cast<const unsigned int*>(dh->data_ptr())           \
+             : nullptr,                                                        \
+      reinterpret_cast<const unsigned int*>(h.data_ptr()),                     \
+      reinterpret_cast<const __hip_bfloat16*>(wc.data_ptr()),                  \
+      inv_rms.data_ptr<float>(),                                               \
+      reinterpret_cast<const unsigned short*>(mask.data_ptr<unsigned char>()), \
+      reinterpret_cast<unsigned int*>(t.data_ptr()),                           \
+      reinterpret_cast<unsigned int*>(dy.data_ptr()), dw.data_ptr<float>(),    \
+      n_rows, d / 2, inv_keep)
+#define LAUNCH_ADDNORM_B_DH(NDW)                                               \
+  do {                                                                         \
+    if (has_dh) LAUNCH_ADDNORM_B(NDW, true);                                   \
+    else LAUNCH_ADDNORM_B(NDW, false);                                         \
+  } while (0)
+  switch (addnorm_ndw(d)) {
+    case 2: LAUNCH_ADDNORM_B_DH(2); break;
+    case 4: LAUNCH_ADDNORM_B_DH(4); break;
+    default: LAUNCH_ADDNORM_B_DH(8); break;
+  }
+#undef LAUNCH_ADDNORM_B_DH
+#undef LAUNCH_ADDNORM_B
+  return {t, dy, rms_dw_finish(dw, n_blocks, d, w, stream)};
 }
 
 std::vector<torch::Tensor> l2norm_fwd(torch::Tensor x, double eps) {

@@ -29,7 +29,7 @@ from torch import Tensor, nn
 
 from genrec_amd import ops
 from genrec_amd.ops.linear import SplitKLinear
-from genrec_amd.modules.norms import RMSNorm
+from genrec_amd.modules.norms import RMSNorm, T5RMSNorm
 
 
 def relative_position_bucket(relative_positions: Tensor, num_buckets: int = 32,
@@ -242,23 +242,65 @@ class TransformerBlock(nn.Module):
                 attn_mask: Optional[Tensor] = None,
                 key_padding_mask: Optional[Tensor] = None,
                 memory_key_padding_mask: Optional[Tensor] = None,
-                kv_cache: Optional[dict] = None) -> Tensor:
+                kv_cache: Optional[dict] = None,
+                normed: Optional[Tensor] = None,
+                next_norm: Optional[nn.Module] = None):
+        """Returns the block output. The two last arguments let a stack
+        fuse across blocks: `normed` is norm1(x) already computed by the
+        previous block, and with `next_norm` (the next block's norm1) the
+        block returns (output, next_norm(output))."""
         self_cache = cross_cache = None
         if kv_cache is not None:
             self_cache = kv_cache.setdefault("self", {})
             cross_cache = kv_cache.setdefault("cross", {})
-        x = ops.dropout_add(self.self_attn(
-            self.norm1(x), attn_mask=attn_mask,
+        if normed is None:
+            normed = self.norm1(x)
+        use_cross = self.cross_attn_enabled and context is not None
+        x, normed = _dropout_add_norm(self.self_attn(
+            normed, attn_mask=attn_mask,
             key_padding_mask=key_padding_mask, kv_cache=self_cache,
-        ), x, self.dropout1.p, self.training)
-        if self.cross_attn_enabled and context is not None:
-            x = ops.dropout_add(self.cross_attn(
-                self.norm_cross(x), key=context, value=context,
+        ), x, self.dropout1.p, self.training,
+            self.norm_cross if use_cross else self.norm2)
+        if use_cross:
+            x, normed = _dropout_add_norm(self.cross_attn(
+                normed, key=context, value=context,
                 key_padding_mask=memory_key_padding_mask, kv_cache=cross_cache,
-            ), x, self.dropout_cross.p, self.training)
-        x = ops.dropout_add(self.ff(self.norm2(x)), x, self.dropout2.p,
-                            self.training)
-        return x
+            ), x, self.dropout_cross.p, self.training, self.norm2)
+        y = self.ff(normed)
+        if next_norm is None:
+            return ops.dropout_add(y, x, self.dropout2.p, self.training)
+        return _dropout_add_norm(y, x, self.dropout2.p, self.training,
+                                 next_norm)
+
+
+def _dropout_add_norm(y: Tensor, x: Tensor, p: float, training: bool,
+                      norm: nn.Module) -> tuple[Tensor, Tensor]:
+    """(h, norm(h)) for h = x + dropout(y): one fused op when `norm` is one
+    of the two RMS classes, the composed pair for any other norm_cls."""
+    if type(norm) is RMSNorm:
+        return ops.dropout_add_rms_norm(y, x, norm.weight, p, norm.eps,
+                                        False, training)
+    if type(norm) is T5RMSNorm:
+        return ops.dropout_add_rms_norm(y, x, norm.weight, p,
+                                        norm.variance_epsilon, True, training)
+    h = ops.dropout_add(y, x, p, training)
+    return h, norm(h)
+
+
+def _run_layers(layers, x: Tensor, kv_caches: Optional[list] = None,
+                **kwargs) -> Tensor:
+    """Run a stack of blocks, handing each block's last residual add to the
+    next block's norm1 so the pair runs fused."""
+    normed = None
+    last = len(layers) - 1
+    for i, layer in enumerate(layers):
+        kv = kv_caches[i] if kv_caches is not None else None
+        if i < last:
+            x, normed = layer(x, kv_cache=kv, normed=normed,
+                              next_norm=layers[i + 1].norm1, **kwargs)
+        else:
+            x = layer(x, kv_cache=kv, normed=normed, **kwargs)
+    return x
 
 
 class TransformerEncoder(nn.Module):
@@ -274,10 +316,8 @@ class TransformerEncoder(nn.Module):
 
     def forward(self, src: Tensor, *, attn_mask: Optional[Tensor] = None,
                 key_padding_mask: Optional[Tensor] = None) -> Tensor:
-        for layer in self.layers:
-            src = layer(src, attn_mask=attn_mask,
-                        key_padding_mask=key_padding_mask)
-        return src
+        return _run_layers(self.layers, src, attn_mask=attn_mask,
+                           key_padding_mask=key_padding_mask)
 
 
 class TransformerDecoder(nn.Module):
@@ -296,12 +336,10 @@ class TransformerDecoder(nn.Module):
                 key_padding_mask: Optional[Tensor] = None,
                 memory_key_padding_mask: Optional[Tensor] = None,
                 kv_caches: Optional[list] = None) -> Tensor:
-        for i, layer in enumerate(self.layers):
-            tgt = layer(tgt, context=memory, attn_mask=attn_mask,
-                        key_padding_mask=key_padding_mask,
-                        memory_key_padding_mask=memory_key_padding_mask,
-                        kv_cache=kv_caches[i] if kv_caches is not None else None)
-        return tgt
+        return _run_layers(self.layers, tgt, kv_caches, context=memory,
+                           attn_mask=attn_mask,
+                           key_padding_mask=key_padding_mask,
+                           memory_key_padding_mask=memory_key_padding_mask)
 
 
 class TransformerEncoderDecoder(nn.Module):

@@ -90,7 +90,9 @@ from genrec_amd.ops.quantize import residual_quantize_step  # noqa: E402
 from genrec_amd.ops.losses import softmax_ce, tied_softmax_ce, summed_ce  # noqa: E402
 from genrec_amd.ops.metrics import topk_hit_ranks  # noqa: E402
 from genrec_amd.ops.embedding import embedding  # noqa: E402
-from genrec_amd.ops.fused import dropout_add, plain_dropout, relu_dropout  # noqa: E402
+from genrec_amd.ops.fused import (  # noqa: E402
+    dropout_add, dropout_add_rms_norm, plain_dropout, relu_dropout,
+)
 
 __all__ = [
     "ext",
@@ -114,6 +116,7 @@ __all__ = [
     "topk_hit_ranks",
     "embedding",
     "dropout_add",
+    "dropout_add_rms_norm",
     "plain_dropout",
     "relu_dropout",
 ]
