@@ -24,17 +24,13 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
-#include "../core/common.h"
+#include "../core/mfma_tile.h"  // idx4, NEG_BIG
 
 namespace genrec {
 
 constexpr int MAXL = 64;   // max Lk per block (wave width)
 constexpr int NWAVES = 8;  // waves per workgroup (512 threads)
 constexpr int MAXD = 64;   // max head dim
-constexpr float NEG_BIG_F = -1e9f;
-
-#define IDX4(b, h, i, j, H, I, J) \
-  ((((int64_t)(b) * (H) + (h)) * (I) + (i)) * (J) + (j))
 
 template <typename T>
 __global__ void attn_fwd_kernel(
@@ -71,13 +67,13 @@ __global__ void attn_fwd_kernel(
   // stage K^T and V (fp32) — coalesced global reads
   for (int idx = tid; idx < Lk * D; idx += blockDim.x) {
     int j = idx / D, t = idx % D;
-    float val = to_f32(k[IDX4(b, h, j, t, H, Lk, D)]);
+    float val = to_f32(k[idx4(b, h, j, t, H, Lk, D)]);
     kt[t * (MAXL + 1) + j] = val;
-    vv[j * MAXD + t] = to_f32(v[IDX4(b, h, j, t, H, Lk, D)]);
+    vv[j * MAXD + t] = to_f32(v[idx4(b, h, j, t, H, Lk, D)]);
   }
   for (int idx = tid; idx < (q1 - q0) * D; idx += blockDim.x) {
     int i = idx / D, t = idx % D;
-    qq[i * MAXD + t] = to_f32(q[IDX4(b, h, q0 + i, t, H, Lq, D)]);
+    qq[i * MAXD + t] = to_f32(q[idx4(b, h, q0 + i, t, H, Lq, D)]);
   }
   __syncthreads();
 
@@ -93,9 +89,9 @@ __global__ void attn_fwd_kernel(
       for (int t = 0; t < D; ++t) s += qr[t] * ktc[t * (MAXL + 1)];
       s *= scale;
       if (bias_dim == 3) s += bias[((int64_t)h * Lq + i) * Lk + lane];
-      else if (bias_dim == 4) s += bias[IDX4(b, h, i, lane, H, Lq, Lk)];
-      if (causal && lane > i) s = NEG_BIG_F;
-      if (key_pad && key_pad[(int64_t)b * Lk + lane]) s = NEG_BIG_F;
+      else if (bias_dim == 4) s += bias[idx4(b, h, i, lane, H, Lq, Lk)];
+      if (causal && lane > i) s = NEG_BIG;
+      if (key_pad && key_pad[(int64_t)b * Lk + lane]) s = NEG_BIG;
       if (add_mask) s += add_mask[(int64_t)i * Lk + lane];
     }
 
@@ -110,12 +106,12 @@ __global__ void attn_fwd_kernel(
       p = col_ok ? s * sigmoidf_dev(s) : 0.f;
     }
     if (col_ok) {
-      p_saved[IDX4(b, h, i, lane, H, Lq, Lk)] = (act == 0) ? p : s;
+      p_saved[idx4(b, h, i, lane, H, Lq, Lk)] = (act == 0) ? p : s;
     }
     // post-softmax query mask (SASRec) then dropout
     if (query_mask) p *= query_mask[(int64_t)b * Lq + i];
     if (dropout_p > 0.f && col_ok) {
-      unsigned long long gidx = IDX4(b, h, i, lane, H, Lq, Lk);
+      unsigned long long gidx = idx4(b, h, i, lane, H, Lq, Lk);
       bool keep = (hash_rng(seed, gidx) & 0xFFFFFF) >=
                   (unsigned int)(dropout_p * 16777216.0f);
       drop_mask[gidx] = keep;
@@ -131,7 +127,7 @@ __global__ void attn_fwd_kernel(
       float acc = 0.f;
       const float* vcol = vv + lane;
       for (int j = 0; j < Lk; ++j) acc += prow[j] * vcol[j * MAXD];
-      out[IDX4(b, h, i, lane, H, Lq, D)] = from_f32<T>(acc);
+      out[idx4(b, h, i, lane, H, Lq, D)] = from_f32<T>(acc);
     }
   }
 }
@@ -172,13 +168,13 @@ __global__ void attn_bwd_kernel(
 
   for (int idx = tid; idx < Lk * D; idx += blockDim.x) {
     int j = idx / D, t = idx % D;
-    vt[t * (MAXL + 1) + j] = to_f32(v[IDX4(b, h, j, t, H, Lk, D)]);
-    kk[j * MAXD + t] = to_f32(k[IDX4(b, h, j, t, H, Lk, D)]);
+    vt[t * (MAXL + 1) + j] = to_f32(v[idx4(b, h, j, t, H, Lk, D)]);
+    kk[j * MAXD + t] = to_f32(k[idx4(b, h, j, t, H, Lk, D)]);
   }
   for (int idx = tid; idx < Lq * D; idx += blockDim.x) {
     int i = idx / D, t = idx % D;
-    qs[i * MAXD + t] = to_f32(q[IDX4(b, h, i, t, H, Lq, D)]);
-    dos[i * MAXD + t] = to_f32(dout[IDX4(b, h, i, t, H, Lq, D)]);
+    qs[i * MAXD + t] = to_f32(q[idx4(b, h, i, t, H, Lq, D)]);
+    dos[i * MAXD + t] = to_f32(dout[idx4(b, h, i, t, H, Lq, D)]);
   }
   // stage P and the combined post-softmax multiplier (query mask x
   // dropout keep/scale) in one coalesced pass — the inner loops then only
@@ -187,11 +183,11 @@ __global__ void attn_bwd_kernel(
   const bool has_am = (query_mask != nullptr) || (dropout_p > 0.f);
   for (int idx = tid; idx < Lq * Lk; idx += blockDim.x) {
     int i = idx / Lk, j = idx % Lk;
-    ps[i * (MAXL + 1) + j] = p_saved[IDX4(b, h, i, j, H, Lq, Lk)];
+    ps[i * (MAXL + 1) + j] = p_saved[idx4(b, h, i, j, H, Lq, Lk)];
     if (has_am) {
       float m = query_mask ? query_mask[(int64_t)b * Lq + i] : 1.f;
       if (dropout_p > 0.f) {
-        m *= drop_mask[IDX4(b, h, i, j, H, Lq, Lk)] ? inv_keep : 0.f;
+        m *= drop_mask[idx4(b, h, i, j, H, Lq, Lk)] ? inv_keep : 0.f;
       }
       am[i * (MAXL + 1) + j] = m;
     }
@@ -221,7 +217,7 @@ __global__ void attn_bwd_kernel(
       ds = col_ok ? dp * sg * (1.f + s * (1.f - sg)) : 0.f;
     }
     if (lane < MAXL) dss[i * (MAXL + 1) + lane] = col_ok ? ds : 0.f;
-    if (ds_out && col_ok) ds_out[IDX4(b, h, i, lane, H, Lq, Lk)] = ds;
+    if (ds_out && col_ok) ds_out[idx4(b, h, i, lane, H, Lq, Lk)] = ds;
   }
   __syncthreads();
 
@@ -232,7 +228,7 @@ __global__ void attn_bwd_kernel(
       const float* dsr = dss + i * (MAXL + 1);
       const float* kc = kk + lane;
       for (int j = 0; j < Lk; ++j) acc += dsr[j] * kc[j * MAXD];
-      dq[IDX4(b, h, i, lane, H, Lq, D)] = from_f32<T>(acc * scale);
+      dq[idx4(b, h, i, lane, H, Lq, D)] = from_f32<T>(acc * scale);
     }
   }
 
@@ -251,8 +247,8 @@ __global__ void attn_bwd_kernel(
         }
         acc_v += a * dos[i * MAXD + lane];
       }
-      dk[IDX4(b, h, j, lane, H, Lk, D)] = from_f32<T>(acc_k * scale);
-      dv[IDX4(b, h, j, lane, H, Lk, D)] = from_f32<T>(acc_v);
+      dk[idx4(b, h, j, lane, H, Lk, D)] = from_f32<T>(acc_k * scale);
+      dv[idx4(b, h, j, lane, H, Lk, D)] = from_f32<T>(acc_v);
     }
   }
 }

@@ -17,43 +17,9 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
-#include "../core/common.h"
+#include "../core/mfma_tile.h"
 
 namespace genrec {
-
-constexpr int FTILE = 64;
-constexpr float FNEG = -1e9f;
-
-typedef __attribute__((ext_vector_type(8))) short short8f;
-typedef __attribute__((ext_vector_type(4))) float float4f;
-
-#define FIDX(b, h, i, j, H, I, J) \
-  ((((int64_t)(b) * (H) + (h)) * (I) + (i)) * (J) + (j))
-
-__device__ __forceinline__ int fswz(int row, int byte_in_row) {
-  return row * 128 + (byte_in_row ^ ((row & 7) << 4));
-}
-
-__device__ __forceinline__ short8f ffrag(const char* base, int row0, int k0,
-                                         int lane) {
-  int row = row0 + (lane & 15);
-  int byte = (k0 + ((lane >> 4) << 3)) * 2;
-  return *reinterpret_cast<const short8f*>(base + fswz(row, byte));
-}
-
-__device__ __forceinline__ void fxpose8x8(short (&vals)[8], int g) {
-#pragma unroll
-  for (int m = 1; m < 8; m <<= 1) {
-    short nv[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      int t = __shfl_xor((int)vals[e ^ m], 8 * m, 64);
-      nv[e] = ((e & m) != (g & m)) ? (short)t : vals[e];
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) vals[e] = nv[e];
-  }
-}
 
 __global__ void __launch_bounds__(256)
 attn_fwd_flash_kernel(
@@ -80,78 +46,60 @@ attn_fwd_flash_kernel(
   const __hip_bfloat16* bias_b = reinterpret_cast<const __hip_bfloat16*>(bias);
   const int bh = blockIdx.x;
   const int b = bh / H, h = bh % H;
-  const int q0 = blockIdx.y * FTILE;
+  const int q0 = blockIdx.y * TILE;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* qs = smem;                  // [64][128B] Q rows
-  char* ks = qs + FTILE * 128;      // [64][128B] K rows (per tile)
-  char* vt = ks + FTILE * 128;      // [64(d)][128B(j)] V^T (per tile)
-  char* ps = vt + FTILE * 128;      // [64][128B] P (per tile)
+  char* qs = smem;                 // [64][128B] Q rows
+  char* ks = qs + TILE * 128;      // [64][128B] K rows (per tile)
+  char* vt = ks + TILE * 128;      // [64(d)][128B(j)] V^T (per tile)
+  char* ps = vt + TILE * 128;      // [64][128B] P (per tile)
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = tid >> 6;
-  const int col_base = lane & 15;
-  const int row_grp = (lane >> 4) << 2;
+  const int col_base = frag_col(lane);
+  const int row_grp = frag_row0(lane);
   const int strip = wid * 16;
   const float inv_keep = dropout_p > 0.f ? 1.0f / (1.0f - dropout_p) : 1.0f;
 
   // ---- stage Q once
-  for (int idx = tid; idx < FTILE * (FTILE / 8); idx += blockDim.x) {
-    int row = idx / (FTILE / 8);
-    int d0 = (idx % (FTILE / 8)) * 8;
-    short8f val = {};
+  for (int idx = tid; idx < TILE * (TILE / 8); idx += blockDim.x) {
+    int row = idx / (TILE / 8);
+    int d0 = (idx % (TILE / 8)) * 8;
     int qi = q0 + row;
-    if (qi < Lq && d0 < D) {
-      val = *reinterpret_cast<const short8f*>(
-          &q[(int64_t)b * q_sb + h * q_sh + qi * q_sl + d0]);
-    }
-    *reinterpret_cast<short8f*>(qs + fswz(row, d0 * 2)) = val;
+    tile_store(qs, row, d0,
+               load8(q, (int64_t)b * q_sb + h * q_sh + qi * q_sl + d0,
+                     qi < Lq && d0 < D));
   }
 
   float m_row[4] = {-1e30f, -1e30f, -1e30f, -1e30f};
   float l_row[4] = {0.f, 0.f, 0.f, 0.f};
-  float4f accO[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+  float4v accO[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
   const int nfrag_d = (D + 15) / 16;
 
-  for (int kt0 = 0; kt0 < Lk; kt0 += FTILE) {
+  for (int kt0 = 0; kt0 < Lk; kt0 += TILE) {
     __syncthreads();  // previous iteration's ps/ks/vt fully consumed
     // ---- stage K tile + V^T tile
-    for (int idx = tid; idx < FTILE * (FTILE / 8); idx += blockDim.x) {
-      int row = idx / (FTILE / 8);
-      int d0 = (idx % (FTILE / 8)) * 8;
+    for (int idx = tid; idx < TILE * (TILE / 8); idx += blockDim.x) {
+      int row = idx / (TILE / 8);
+      int d0 = (idx % (TILE / 8)) * 8;
       int kj = kt0 + row;
-      short8f val = {};
-      if (kj < Lk && d0 < D) {
-        val = *reinterpret_cast<const short8f*>(
-            &k[(int64_t)b * k_sb + h * k_sh + kj * k_sl + d0]);
-      }
-      *reinterpret_cast<short8f*>(ks + fswz(row, d0 * 2)) = val;
-      short8f vv = {};
-      if (kj < Lk && d0 < D) {
-        vv = *reinterpret_cast<const short8f*>(
-            &v[(int64_t)b * v_sb + h * v_sh + kj * v_sl + d0]);
-      }
-      const int g = (lane >> 3) & 7;
-      short tv[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) tv[e] = vv[e];
-      fxpose8x8(tv, g);
-      short8f pack;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) pack[e] = tv[e];
-      *reinterpret_cast<short8f*>(vt + fswz(d0 + g, (row & ~7) * 2)) = pack;
+      const bool ok = kj < Lk && d0 < D;
+      tile_store(ks, row, d0,
+                 load8(k, (int64_t)b * k_sb + h * k_sh + kj * k_sl + d0, ok));
+      tile_store_tr(
+          vt, row, d0, lane,
+          load8(v, (int64_t)b * v_sb + h * v_sh + kj * v_sl + d0, ok));
     }
     __syncthreads();
 
     // ---- S = Q K_t^T
-    float4f acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    float4v acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
       for (int kk = 0; kk < D; kk += 32) {
-        acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            ffrag(qs, strip, kk, lane), ffrag(ks, f * 16, kk, lane), acc[f],
-            0, 0, 0);
+        acc[f] = mfma_bf16(frag_load(qs, strip, kk, lane),
+                           frag_load(ks, f * 16, kk, lane), acc[f]);
       }
     }
 
@@ -168,13 +116,13 @@ attn_fwd_flash_kernel(
           s *= scale;
           if (bias_dim) {
             int64_t bi = (bias_dim == 3) ? ((int64_t)h * Lq + i) * Lk + j
-                                         : FIDX(b, h, i, j, H, Lq, Lk);
+                                         : idx4(b, h, i, j, H, Lq, Lk);
             s += bias_bf16 ? to_f32(bias_b[bi]) : bias_f[bi];
           }
-          if (causal && j > i) s = FNEG;
-          if (key_pad && key_pad[(int64_t)b * Lk + j]) s = FNEG;
+          if (causal && j > i) s = NEG_BIG;
+          if (key_pad && key_pad[(int64_t)b * Lk + j]) s = NEG_BIG;
           if (add_mask) s += add_mask[(int64_t)i * Lk + j];
-          s_saved[FIDX(b, h, i, j, H, Lq, Lk)] = s;
+          s_saved[idx4(b, h, i, j, H, Lq, Lk)] = s;
         } else {
           s = -INFINITY;
         }
@@ -184,11 +132,8 @@ attn_fwd_flash_kernel(
 
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      float tmax = fmaxf(fmaxf(s_val[0][r], s_val[1][r]),
-                         fmaxf(s_val[2][r], s_val[3][r]));
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1)
-        tmax = fmaxf(tmax, __shfl_xor(tmax, off, 64));
+      float tmax = grp16_max(fmaxf(fmaxf(s_val[0][r], s_val[1][r]),
+                                   fmaxf(s_val[2][r], s_val[3][r])));
       float m_new = fmaxf(m_row[r], fmaxf(tmax, -1e30f));
       float a = __expf(m_row[r] - m_new);
       float sum = 0.f;
@@ -199,10 +144,7 @@ attn_fwd_flash_kernel(
         s_val[f][r] = p;  // reuse as unnormalized p
         sum += p;
       }
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1)
-        sum += __shfl_xor(sum, off, 64);
-      l_row[r] = l_row[r] * a + sum;
+      l_row[r] = l_row[r] * a + grp16_sum(sum);
       m_row[r] = m_new;
       // rescale accumulated O for this row
 #pragma unroll
@@ -218,15 +160,13 @@ attn_fwd_flash_kernel(
         int j = kt0 + f * 16 + col_base;
         float p = s_val[f][r];
         if (i < Lq && j < Lk && dropout_p > 0.f) {
-          unsigned long long gidx = FIDX(b, h, i, j, H, Lq, Lk);
+          unsigned long long gidx = idx4(b, h, i, j, H, Lq, Lk);
           bool keep = (hash_rng(seed, gidx) & 0xFFFFFF) >=
                       (unsigned int)(dropout_p * 16777216.0f);
           drop_mask[gidx] = keep;
           p = keep ? p * inv_keep : 0.f;
         }
-        int row = strip + row_grp + r;
-        *reinterpret_cast<__hip_bfloat16*>(ps + fswz(row, (j - kt0) * 2)) =
-            __float2bfloat16(p);
+        tile_store(ps, strip + row_grp + r, j - kt0, bf16_bits(p));
       }
     }
     __builtin_amdgcn_wave_barrier();
@@ -235,10 +175,9 @@ attn_fwd_flash_kernel(
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
       if (f >= nfrag_d) break;
-      for (int kk = 0; kk < FTILE; kk += 32) {
-        accO[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            ffrag(ps, strip, kk, lane), ffrag(vt, f * 16, kk, lane), accO[f],
-            0, 0, 0);
+      for (int kk = 0; kk < TILE; kk += 32) {
+        accO[f] = mfma_bf16(frag_load(ps, strip, kk, lane),
+                            frag_load(vt, f * 16, kk, lane), accO[f]);
       }
     }
   }
@@ -255,7 +194,7 @@ attn_fwd_flash_kernel(
         float inv = (l_row[r] > 0.f) ? 1.0f / l_row[r] : 0.f;
         float o = accO[f][r] * inv;
         if (query_mask) o *= query_mask[(int64_t)b * Lq + i];
-        out[FIDX(b, h, i, d, H, Lq, D)] = __float2bfloat16(o);
+        out[idx4(b, h, i, d, H, Lq, D)] = __float2bfloat16(o);
       }
     }
   }
@@ -297,101 +236,77 @@ attn_bwd_flash_kernel(
     int64_t v_sb, int64_t v_sh, int64_t v_sl) {
   const int bh = blockIdx.x;
   const int b = bh / H, h = bh % H;
-  const int kt0 = blockIdx.y * FTILE;
+  const int kt0 = blockIdx.y * TILE;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* vs = smem;                  // [64][128B] V_t rows (persistent)
-  char* kt = vs + FTILE * 128;      // [64(d)][128B(j)] K_t^T (persistent)
-  char* dos = kt + FTILE * 128;     // [64][128B] dO rows (per q-tile)
-  char* qt = dos + FTILE * 128;     // [64(d)][128B(i)] Q^T (per q-tile)
-  char* dot = qt + FTILE * 128;     // [64(d)][128B(i)] dO^T (per q-tile)
-  char* dsn = dot + FTILE * 128;    // [64(i)][128B(j)] dS
-  char* dst = dsn + FTILE * 128;    // [64(j)][128B(i)] dS^T
-  char* adt = dst + FTILE * 128;    // [64(j)][128B(i)] A_d^T
+  char* vs = smem;                 // [64][128B] V_t rows (persistent)
+  char* kt = vs + TILE * 128;      // [64(d)][128B(j)] K_t^T (persistent)
+  char* dos = kt + TILE * 128;     // [64][128B] dO rows (per q-tile)
+  char* qt = dos + TILE * 128;     // [64(d)][128B(i)] Q^T (per q-tile)
+  char* dot = qt + TILE * 128;     // [64(d)][128B(i)] dO^T (per q-tile)
+  char* dsn = dot + TILE * 128;    // [64(i)][128B(j)] dS
+  char* dst = dsn + TILE * 128;    // [64(j)][128B(i)] dS^T
+  char* adt = dst + TILE * 128;    // [64(j)][128B(i)] A_d^T
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = tid >> 6;
-  const int col_base = lane & 15;
-  const int row_grp = (lane >> 4) << 2;
+  const int col_base = frag_col(lane);
+  const int row_grp = frag_row0(lane);
   const int strip = wid * 16;
   const int i0g = strip + row_grp;  // 8B-aligned store base (see mfma bwd)
   const float inv_keep = dropout_p > 0.f ? 1.0f / (1.0f - dropout_p) : 1.0f;
-  typedef __attribute__((ext_vector_type(4))) short short4f;
 
   // ---- stage V_t natural + K_t^T once
-  for (int idx = tid; idx < FTILE * (FTILE / 8); idx += blockDim.x) {
-    int row = idx / (FTILE / 8);
-    int d0 = (idx % (FTILE / 8)) * 8;
+  for (int idx = tid; idx < TILE * (TILE / 8); idx += blockDim.x) {
+    int row = idx / (TILE / 8);
+    int d0 = (idx % (TILE / 8)) * 8;
     int kj = kt0 + row;
-    short8f val = {};
-    short8f kk8 = {};
-    if (kj < Lk && d0 < D) {
-      val = *reinterpret_cast<const short8f*>(
-          &v[(int64_t)b * v_sb + h * v_sh + kj * v_sl + d0]);
-      kk8 = *reinterpret_cast<const short8f*>(
-          &k[(int64_t)b * k_sb + h * k_sh + kj * k_sl + d0]);
-    }
-    *reinterpret_cast<short8f*>(vs + fswz(row, d0 * 2)) = val;
-    const int g = (lane >> 3) & 7;
-    short tk[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) tk[e] = kk8[e];
-    fxpose8x8(tk, g);
-    short8f pk;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) pk[e] = tk[e];
-    *reinterpret_cast<short8f*>(kt + fswz(d0 + g, (row & ~7) * 2)) = pk;
+    const bool ok = kj < Lk && d0 < D;
+    short8v vv8 = load8(
+        v, (int64_t)b * v_sb + h * v_sh + kj * v_sl + d0, ok);
+    short8v kk8 = load8(
+        k, (int64_t)b * k_sb + h * k_sh + kj * k_sl + d0, ok);
+    tile_store(vs, row, d0, vv8);
+    tile_store_tr(kt, row, d0, lane, kk8);
   }
 
   const int nfrag_d = (D + 15) / 16;
-  float4f acck[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-  float4f accv[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+  float4v acck[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+  float4v accv[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
 
-  for (int q0 = 0; q0 < Lq; q0 += FTILE) {
+  for (int q0 = 0; q0 < Lq; q0 += TILE) {
     __syncthreads();
     // ---- stage dO natural + dO^T + Q^T for this q-tile
-    for (int idx = tid; idx < FTILE * (FTILE / 8); idx += blockDim.x) {
-      int row = idx / (FTILE / 8);
-      int d0 = (idx % (FTILE / 8)) * 8;
+    for (int idx = tid; idx < TILE * (TILE / 8); idx += blockDim.x) {
+      int row = idx / (TILE / 8);
+      int d0 = (idx % (TILE / 8)) * 8;
       int qi = q0 + row;
-      short8f dd8 = {}, qq8 = {};
-      if (qi < Lq && d0 < D) {
-        dd8 = *reinterpret_cast<const short8f*>(
-            &dout[(int64_t)b * do_sb + h * do_sh + qi * do_sl + d0]);
-        qq8 = *reinterpret_cast<const short8f*>(
-            &q[(int64_t)b * q_sb + h * q_sh + qi * q_sl + d0]);
-      }
-      *reinterpret_cast<short8f*>(dos + fswz(row, d0 * 2)) = dd8;
-      const int g = (lane >> 3) & 7;
-      short td[8], tq[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { td[e] = dd8[e]; tq[e] = qq8[e]; }
-      fxpose8x8(td, g);
-      fxpose8x8(tq, g);
-      short8f pd, pq;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { pd[e] = td[e]; pq[e] = tq[e]; }
-      *reinterpret_cast<short8f*>(dot + fswz(d0 + g, (row & ~7) * 2)) = pd;
-      *reinterpret_cast<short8f*>(qt + fswz(d0 + g, (row & ~7) * 2)) = pq;
+      const bool ok = qi < Lq && d0 < D;
+      short8v dd8 = load8(
+          dout, (int64_t)b * do_sb + h * do_sh + qi * do_sl + d0, ok);
+      short8v qq8 = load8(
+          q, (int64_t)b * q_sb + h * q_sh + qi * q_sl + d0, ok);
+      tile_store(dos, row, d0, dd8);
+      tile_store_tr(dot, row, d0, lane, dd8);
+      tile_store_tr(qt, row, d0, lane, qq8);
     }
     __syncthreads();
 
     // ---- dA = dO V_t^T : C rows = q rows (this wave's strip)
-    float4f acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    float4v acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
       for (int kk = 0; kk < D; kk += 32) {
-        acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            ffrag(dos, strip, kk, lane), ffrag(vs, f * 16, kk, lane), acc[f],
-            0, 0, 0);
+        acc[f] = mfma_bf16(frag_load(dos, strip, kk, lane),
+                           frag_load(vs, f * 16, kk, lane), acc[f]);
       }
     }
 
     // ---- epilogue: reconstruct P, dS = P (M*dA - dot_i); stash tiles
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
-      short4f dpack, apack;
+      short4v dpack, apack;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         int i = q0 + strip + row_grp + r;
@@ -400,43 +315,38 @@ attn_bwd_flash_kernel(
         if (i < Lq && j < Lk) {
           float m = ml_saved[((int64_t)bh * Lq + i) * 2 + 0];
           float l = ml_saved[((int64_t)bh * Lq + i) * 2 + 1];
-          float s = s_saved[FIDX(b, h, i, j, H, Lq, Lk)];
+          float s = s_saved[idx4(b, h, i, j, H, Lq, Lk)];
           float p = (l > 0.f) ? __expf(s - m) / l : 0.f;
           float mult = 1.f;
           if (query_mask) mult *= query_mask[(int64_t)b * Lq + i];
           if (dropout_p > 0.f) {
-            mult *= drop_mask[FIDX(b, h, i, j, H, Lq, Lk)] ? inv_keep : 0.f;
+            mult *= drop_mask[idx4(b, h, i, j, H, Lq, Lk)] ? inv_keep : 0.f;
           }
           float dp = acc[f][r] * mult;
           dval = p * (dp - dot_row[(int64_t)bh * Lq + i]);
           aval = p * mult;
-          if (ds_saved) ds_saved[FIDX(b, h, i, j, H, Lq, Lk)] = dval;
+          if (ds_saved) ds_saved[idx4(b, h, i, j, H, Lq, Lk)] = dval;
         }
-        __hip_bfloat16 dh = __float2bfloat16(dval * scale);
-        __hip_bfloat16 ah = __float2bfloat16(aval);
-        dpack[r] = *reinterpret_cast<short*>(&dh);
-        apack[r] = *reinterpret_cast<short*>(&ah);
-        int row = strip + row_grp + r;
-        *reinterpret_cast<__hip_bfloat16*>(
-            dsn + fswz(row, (f * 16 + col_base) * 2)) = dh;
+        dpack[r] = bf16_bits(dval * scale);
+        apack[r] = bf16_bits(aval);
+        tile_store(dsn, strip + row_grp + r, f * 16 + col_base, dpack[r]);
       }
       int jl = f * 16 + col_base;  // tile-local j row of the transposed tiles
-      *reinterpret_cast<short4f*>(dst + fswz(jl, i0g * 2)) = dpack;
-      *reinterpret_cast<short4f*>(adt + fswz(jl, i0g * 2)) = apack;
+      tile_store(dst, jl, i0g, dpack);
+      tile_store(adt, jl, i0g, apack);
     }
     // dQ uses only this wave's dS rows
     __builtin_amdgcn_wave_barrier();
 
     {  // dQ[strip rows of this q-tile] += (scale*dS) @ K_t  (atomic fp32)
-      float4f accq[4] = {{0, 0, 0, 0}, {0, 0, 0, 0},
+      float4v accq[4] = {{0, 0, 0, 0}, {0, 0, 0, 0},
                          {0, 0, 0, 0}, {0, 0, 0, 0}};
 #pragma unroll
       for (int f = 0; f < 4; ++f) {
         if (f >= nfrag_d) break;
-        for (int kk = 0; kk < FTILE; kk += 32) {
-          accq[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              ffrag(dsn, strip, kk, lane), ffrag(kt, f * 16, kk, lane),
-              accq[f], 0, 0, 0);
+        for (int kk = 0; kk < TILE; kk += 32) {
+          accq[f] = mfma_bf16(frag_load(dsn, strip, kk, lane),
+                              frag_load(kt, f * 16, kk, lane), accq[f]);
         }
       }
 #pragma unroll
@@ -447,7 +357,7 @@ attn_bwd_flash_kernel(
           int i = q0 + strip + row_grp + r;
           int d = f * 16 + col_base;
           if (i < Lq && d < D) {
-            atomicAdd(&dq_f32[FIDX(b, h, i, d, H, Lq, D)], accq[f][r]);
+            atomicAdd(&dq_f32[idx4(b, h, i, d, H, Lq, D)], accq[f][r]);
           }
         }
       }
@@ -458,13 +368,11 @@ attn_bwd_flash_kernel(
 #pragma unroll
       for (int f = 0; f < 4; ++f) {
         if (f >= nfrag_d) break;
-        for (int kk = 0; kk < FTILE; kk += 32) {
-          acck[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              ffrag(dst, strip, kk, lane), ffrag(qt, f * 16, kk, lane),
-              acck[f], 0, 0, 0);
-          accv[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              ffrag(adt, strip, kk, lane), ffrag(dot, f * 16, kk, lane),
-              accv[f], 0, 0, 0);
+        for (int kk = 0; kk < TILE; kk += 32) {
+          acck[f] = mfma_bf16(frag_load(dst, strip, kk, lane),
+                              frag_load(qt, f * 16, kk, lane), acck[f]);
+          accv[f] = mfma_bf16(frag_load(adt, strip, kk, lane),
+                              frag_load(dot, f * 16, kk, lane), accv[f]);
         }
       }
     }
@@ -479,8 +387,8 @@ attn_bwd_flash_kernel(
       int j = kt0 + strip + row_grp + r;
       int d = f * 16 + col_base;
       if (j < Lk && d < D) {
-        dk_out[FIDX(b, h, j, d, H, Lk, D)] = __float2bfloat16(acck[f][r]);
-        dv_out[FIDX(b, h, j, d, H, Lk, D)] = __float2bfloat16(accv[f][r]);
+        dk_out[idx4(b, h, j, d, H, Lk, D)] = __float2bfloat16(acck[f][r]);
+        dv_out[idx4(b, h, j, d, H, Lk, D)] = __float2bfloat16(accv[f][r]);
       }
     }
   }
@@ -498,7 +406,7 @@ std::vector<torch::Tensor> attn_fwd_flash(
   TORCH_CHECK(q.scalar_type() == torch::kBFloat16);
   const int B = q.size(0), H = q.size(1), Lq = q.size(2), D = q.size(3);
   const int Lk = k.size(2);
-  TORCH_CHECK(D <= FTILE && D % 32 == 0);
+  TORCH_CHECK(D <= TILE && D % 32 == 0);
   // stride-aware over [B,H,L,D] views (d must be innermost; 16-byte
   // short8 loads need 8-element-aligned batch/head/row strides — true
   // for every [B,L,H,D] transpose view at D % 32 == 0). Anything else
@@ -533,8 +441,8 @@ std::vector<torch::Tensor> attn_fwd_flash(
   if (query_mask.has_value())
     qm_f = query_mask->to(torch::kFloat32).contiguous();
   dim3 block(256);
-  dim3 grid(B * H, (Lq + FTILE - 1) / FTILE);
-  size_t smem = 4 * FTILE * 128;
+  dim3 grid(B * H, (Lq + TILE - 1) / TILE);
+  size_t smem = 4 * TILE * 128;
   auto stream = at::cuda::getCurrentHIPStream();
   hipLaunchKernelGGL(attn_fwd_flash_kernel, grid, block, smem, stream,
       reinterpret_cast<const __hip_bfloat16*>(qn.data_ptr()),
@@ -591,8 +499,8 @@ std::vector<torch::Tensor> attn_bwd_flash(
   if (query_mask.has_value())
     qm_f = query_mask->to(torch::kFloat32).contiguous();
   dim3 block(256);
-  dim3 grid(B * H, (Lk + FTILE - 1) / FTILE);
-  size_t smem = 8 * FTILE * 128;
+  dim3 grid(B * H, (Lk + TILE - 1) / TILE);
+  size_t smem = 8 * TILE * 128;
   auto stream = at::cuda::getCurrentHIPStream();
   hipLaunchKernelGGL(attn_bwd_flash_kernel, grid, block, smem, stream,
       reinterpret_cast<const __hip_bfloat16*>(don.data_ptr()),

@@ -30,56 +30,11 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
-#include "../core/common.h"
+#include "../core/mfma_tile.h"
 
 namespace genrec {
 
 namespace {
-
-constexpr int GT = 64;  // tile rows (queries and keys)
-
-// LDS is accessed through may_alias types: tiles are written with one
-// vector width and read back with another.
-typedef __attribute__((ext_vector_type(8))) short g_short8;
-typedef __attribute__((ext_vector_type(4))) short g_short4;
-typedef __attribute__((ext_vector_type(4))) float g_float4;
-typedef g_short8 __attribute__((may_alias)) g_short8a;
-typedef g_short4 __attribute__((may_alias)) g_short4a;
-typedef short __attribute__((may_alias)) g_short1a;
-
-// XOR swizzle on 16-byte slots; rs = row stride in bytes (128 or 256).
-__device__ __forceinline__ int gswz(int row, int byte_in_row, int rs) {
-  return row * rs + (byte_in_row ^ ((row & 7) << 4));
-}
-
-__device__ __forceinline__ g_short8 gfrag(const char* base, int row0, int k0,
-                                          int lane, int rs) {
-  int row = row0 + (lane & 15);
-  int byte = (k0 + ((lane >> 4) << 3)) * 2;
-  return *reinterpret_cast<const g_short8a*>(base + gswz(row, byte, rs));
-}
-
-// In-register 8x8 transpose across the 8 lanes {lane ^ 8, ^ 16, ^ 32} (as
-// xpose8x8 in attention_flash.hip). A variant that exchanges only the four
-// replaced elements per stage, packed two per shuffle, measured slower.
-__device__ __forceinline__ void gxpose8x8(short (&vals)[8], int g) {
-#pragma unroll
-  for (int m = 1; m < 8; m <<= 1) {
-    short nv[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      int t = __shfl_xor((int)vals[e ^ m], 8 * m, 64);
-      nv[e] = ((e & m) != (g & m)) ? (short)t : vals[e];
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) vals[e] = nv[e];
-  }
-}
-
-__device__ __forceinline__ short bf16_bits(float x) {
-  __hip_bfloat16 h = __float2bfloat16(x);
-  return *reinterpret_cast<short*>(&h);
-}
 
 // Stage 64 rows x D of a [*, L, D]-strided operand (row stride sl) into a
 // natural tile nat[64][D] and/or a transposed tile tr[D][64]. Rows at or
@@ -92,31 +47,15 @@ __device__ __forceinline__ void gstage(const __hip_bfloat16* __restrict__ src,
                                        int64_t sl, int r0, int L, char* nat,
                                        char* tr, int tid) {
   const int lane = tid & 63;
-  for (int idx = tid; idx < GT * (D / 8); idx += 256) {
+  for (int idx = tid; idx < TILE * (D / 8); idx += 256) {
     int half = idx >> 9;          // 512 items per 64-column half
     int rem = idx & 511;
     int row = rem >> 3;
     int d0 = half * 64 + (rem & 7) * 8;
     int gi = r0 + row;
-    g_short8 val = {};
-    if (gi < L) {
-      val = *reinterpret_cast<const g_short8*>(&src[(int64_t)gi * sl + d0]);
-    }
-    if (NAT) {
-      *reinterpret_cast<g_short8a*>(nat + gswz(row, d0 * 2, D * 2)) = val;
-    }
-    if (TR) {
-      const int g = (lane >> 3) & 7;  // == row & 7
-      short t[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) t[e] = val[e];
-      gxpose8x8(t, g);
-      g_short8 pack;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) pack[e] = t[e];
-      *reinterpret_cast<g_short8a*>(tr + gswz(d0 + g, (row & ~7) * 2, 128)) =
-          pack;
-    }
+    short8v val = load8(src, (int64_t)gi * sl + d0, gi < L);
+    if (NAT) tile_store(nat, row, d0, val, D * 2);
+    if (TR) tile_store_tr(tr, row, d0, lane, val);
   }
 }
 
@@ -137,54 +76,53 @@ gqa_fwd_kernel(const __hip_bfloat16* __restrict__ q,
   constexpr int RS = D * 2;
   const int b = blockIdx.x / Hq, h = blockIdx.x % Hq;
   const int hk = h / (Hq / Hkv);
-  const int q0 = blockIdx.y * GT;
+  const int q0 = blockIdx.y * TILE;
   const int off = Lk - Lq;  // query row i sits at absolute position i + off
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* qs = smem;             // [64][D]   Q rows
-  char* ks = qs + GT * RS;     // [64][D]   K rows (per tile)
-  char* vt = ks + GT * RS;     // [D][64]   V^T (per tile)
-  char* ps = vt + D * 128;     // [64][64]  P (per tile)
+  char* qs = smem;               // [64][D]   Q rows
+  char* ks = qs + TILE * RS;     // [64][D]   K rows (per tile)
+  char* vt = ks + TILE * RS;     // [D][64]   V^T (per tile)
+  char* ps = vt + D * 128;       // [64][64]  P (per tile)
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = tid >> 6;
-  const int col_base = lane & 15;
-  const int row_grp = (lane >> 4) << 2;
+  const int col_base = frag_col(lane);
+  const int row_grp = frag_row0(lane);
   const int strip = wid * 16;
 
   gstage<D, true, false>(q + (int64_t)b * q_sb + (int64_t)h * q_sh, q_sl, q0,
                          Lq, qs, nullptr, tid);
 
   float m_row[4], l_row[4];
-  g_float4 accO[D / 16];
+  float4v accO[D / 16];
 #pragma unroll
   for (int r = 0; r < 4; ++r) { m_row[r] = -INFINITY; l_row[r] = 0.f; }
 #pragma unroll
-  for (int f = 0; f < D / 16; ++f) accO[f] = g_float4{0, 0, 0, 0};
+  for (int f = 0; f < D / 16; ++f) accO[f] = float4v{0, 0, 0, 0};
 
   // K tiles wholly beyond the diagonal of this Q tile are skipped
   int kt_end = Lk;
-  if (causal) kt_end = min(Lk, q0 + GT + off);
+  if (causal) kt_end = min(Lk, q0 + TILE + off);
   const __hip_bfloat16* kb = k + (int64_t)b * k_sb + (int64_t)hk * k_sh;
   const __hip_bfloat16* vb = v + (int64_t)b * v_sb + (int64_t)hk * v_sh;
 
-  for (int kt0 = 0; kt0 < kt_end; kt0 += GT) {
+  for (int kt0 = 0; kt0 < kt_end; kt0 += TILE) {
     __syncthreads();  // previous iteration's ks/vt fully consumed
     gstage<D, true, false>(kb, k_sl, kt0, Lk, ks, nullptr, tid);
     gstage<D, false, true>(vb, v_sl, kt0, Lk, nullptr, vt, tid);
     __syncthreads();
 
     // ---- S = Q K_t^T
-    g_float4 acc[4];
+    float4v acc[4];
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
-      acc[f] = g_float4{0, 0, 0, 0};
+      acc[f] = float4v{0, 0, 0, 0};
 #pragma unroll
       for (int kk = 0; kk < D; kk += 32) {
-        acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            gfrag(qs, strip, kk, lane, RS), gfrag(ks, f * 16, kk, lane, RS),
-            acc[f], 0, 0, 0);
+        acc[f] = mfma_bf16(frag_load(qs, strip, kk, lane, RS),
+                           frag_load(ks, f * 16, kk, lane, RS), acc[f]);
       }
     }
 
@@ -207,11 +145,8 @@ gqa_fwd_kernel(const __hip_bfloat16* __restrict__ q,
     // m = -inf, l = 0 and contributes nothing (no exp(-inf - -inf))
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      float tmax = fmaxf(fmaxf(s_val[0][r], s_val[1][r]),
-                         fmaxf(s_val[2][r], s_val[3][r]));
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1)
-        tmax = fmaxf(tmax, __shfl_xor(tmax, o, 64));
+      float tmax = grp16_max(fmaxf(fmaxf(s_val[0][r], s_val[1][r]),
+                                   fmaxf(s_val[2][r], s_val[3][r])));
       float m_new = fmaxf(m_row[r], tmax);
       bool dead = (m_new == -INFINITY);
       float a = (dead || m_row[r] == -INFINITY) ? (dead ? 1.f : 0.f)
@@ -224,9 +159,7 @@ gqa_fwd_kernel(const __hip_bfloat16* __restrict__ q,
         s_val[f][r] = p;  // reuse as unnormalized p
         sum += p;
       }
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) sum += __shfl_xor(sum, o, 64);
-      l_row[r] = l_row[r] * a + sum;
+      l_row[r] = l_row[r] * a + grp16_sum(sum);
       m_row[r] = m_new;
 #pragma unroll
       for (int f = 0; f < D / 16; ++f) accO[f][r] *= a;
@@ -237,10 +170,8 @@ gqa_fwd_kernel(const __hip_bfloat16* __restrict__ q,
     for (int f = 0; f < 4; ++f) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        int row = strip + row_grp + r;
-        *reinterpret_cast<g_short1a*>(
-            ps + gswz(row, (f * 16 + col_base) * 2, 128)) =
-            bf16_bits(s_val[f][r]);
+        tile_store(ps, strip + row_grp + r, f * 16 + col_base,
+                   bf16_bits(s_val[f][r]));
       }
     }
     __builtin_amdgcn_wave_barrier();
@@ -249,10 +180,9 @@ gqa_fwd_kernel(const __hip_bfloat16* __restrict__ q,
 #pragma unroll
     for (int f = 0; f < D / 16; ++f) {
 #pragma unroll
-      for (int kk = 0; kk < GT; kk += 32) {
-        accO[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            gfrag(ps, strip, kk, lane, 128), gfrag(vt, f * 16, kk, lane, 128),
-            accO[f], 0, 0, 0);
+      for (int kk = 0; kk < TILE; kk += 32) {
+        accO[f] = mfma_bf16(frag_load(ps, strip, kk, lane),
+                            frag_load(vt, f * 16, kk, lane), accO[f]);
       }
     }
     __builtin_amdgcn_wave_barrier();
@@ -294,9 +224,9 @@ gqa_delta_kernel(const __hip_bfloat16* __restrict__ dout,  // [B,Lq,Hq,D] view
     int64_t bh = row / Lq;
     int h = bh % Hq;
     int64_t b = bh / Hq;
-    g_short8 a = *reinterpret_cast<const g_short8*>(
+    short8v a = *reinterpret_cast<const short8v*>(
         &dout[b * do_sb + (int64_t)h * do_sh + (int64_t)i * do_sl + c]);
-    g_short8 o = *reinterpret_cast<const g_short8*>(
+    short8v o = *reinterpret_cast<const short8v*>(
         &out[((b * Lq + i) * Hq + h) * D + c]);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -346,24 +276,24 @@ gqa_bwd_dkdv_kernel(const __hip_bfloat16* __restrict__ dout,
   constexpr int RS = D * 2;
   const int b = blockIdx.x / Hkv, hk = blockIdx.x % Hkv;
   const int grp = Hq / Hkv;
-  const int kt0 = blockIdx.y * GT;
+  const int kt0 = blockIdx.y * TILE;
   const int off = Lk - Lq;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* ks = smem;              // [64][D]  K_t rows (persistent)
-  char* vs = ks + GT * RS;      // [64][D]  V_t rows (persistent)
-  char* qs = vs + GT * RS;      // [64][D]  Q rows (per q-tile)
-  char* dos = qs + GT * RS;     // [64][D]  dO rows (per q-tile)
-  char* qt = dos + GT * RS;     // [D][64]  Q^T
-  char* dot = qt + D * 128;     // [D][64]  dO^T
-  char* dst = dot + D * 128;    // [64 j][64 i]  (scale*dS)^T
-  char* pt = dst + GT * 128;    // [64 j][64 i]  P^T
+  char* ks = smem;                // [64][D]  K_t rows (persistent)
+  char* vs = ks + TILE * RS;      // [64][D]  V_t rows (persistent)
+  char* qs = vs + TILE * RS;      // [64][D]  Q rows (per q-tile)
+  char* dos = qs + TILE * RS;     // [64][D]  dO rows (per q-tile)
+  char* qt = dos + TILE * RS;     // [D][64]  Q^T
+  char* dot = qt + D * 128;       // [D][64]  dO^T
+  char* dst = dot + D * 128;      // [64 j][64 i]  (scale*dS)^T
+  char* pt = dst + TILE * 128;    // [64 j][64 i]  P^T
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = tid >> 6;
-  const int col_base = lane & 15;
-  const int row_grp = (lane >> 4) << 2;
+  const int col_base = frag_col(lane);
+  const int row_grp = frag_row0(lane);
   const int strip = wid * 16;
   const int i0g = strip + row_grp;  // 8-byte aligned store base
 
@@ -381,23 +311,23 @@ gqa_bwd_dkdv_kernel(const __hip_bfloat16* __restrict__ dout,
     if (jok[f] && key_pad) jok[f] = !key_pad[(int64_t)b * Lk + jcol[f]];
   }
 
-  g_float4 acck[D / 16], accv[D / 16];
+  float4v acck[D / 16], accv[D / 16];
 #pragma unroll
   for (int f = 0; f < D / 16; ++f) {
-    acck[f] = g_float4{0, 0, 0, 0};
-    accv[f] = g_float4{0, 0, 0, 0};
+    acck[f] = float4v{0, 0, 0, 0};
+    accv[f] = float4v{0, 0, 0, 0};
   }
 
   // Q tiles whose every row sits before this K tile see none of it
   int q_begin = 0;
-  if (causal && kt0 - off > 0) q_begin = ((kt0 - off) / GT) * GT;
+  if (causal && kt0 - off > 0) q_begin = ((kt0 - off) / TILE) * TILE;
 
   for (int hh = 0; hh < grp; ++hh) {
     const int h = hk * grp + hh;
     const __hip_bfloat16* qb = q + (int64_t)b * q_sb + (int64_t)h * q_sh;
     const __hip_bfloat16* dob = dout + (int64_t)b * do_sb + (int64_t)h * do_sh;
     const int64_t rowb = ((int64_t)b * Hq + h) * Lq;
-    for (int q0 = q_begin; q0 < Lq; q0 += GT) {
+    for (int q0 = q_begin; q0 < Lq; q0 += TILE) {
       __syncthreads();  // previous tile's qs/dos/qt/dot/dst/pt consumed
       gstage<D, true, true>(qb, q_sl, q0, Lq, qs, qt, tid);
       gstage<D, true, true>(dob, do_sl, q0, Lq, dos, dot, tid);
@@ -412,26 +342,24 @@ gqa_bwd_dkdv_kernel(const __hip_bfloat16* __restrict__ dout,
       }
 
       // ---- S = Q K_t^T, dP = dO V_t^T (rows = this wave's q strip)
-      g_float4 acc[4], accp[4];
+      float4v acc[4], accp[4];
 #pragma unroll
       for (int f = 0; f < 4; ++f) {
-        acc[f] = g_float4{0, 0, 0, 0};
-        accp[f] = g_float4{0, 0, 0, 0};
+        acc[f] = float4v{0, 0, 0, 0};
+        accp[f] = float4v{0, 0, 0, 0};
 #pragma unroll
         for (int kk = 0; kk < D; kk += 32) {
-          acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              gfrag(qs, strip, kk, lane, RS), gfrag(ks, f * 16, kk, lane, RS),
-              acc[f], 0, 0, 0);
-          accp[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              gfrag(dos, strip, kk, lane, RS),
-              gfrag(vs, f * 16, kk, lane, RS), accp[f], 0, 0, 0);
+          acc[f] = mfma_bf16(frag_load(qs, strip, kk, lane, RS),
+                             frag_load(ks, f * 16, kk, lane, RS), acc[f]);
+          accp[f] = mfma_bf16(frag_load(dos, strip, kk, lane, RS),
+                              frag_load(vs, f * 16, kk, lane, RS), accp[f]);
         }
       }
 
       // ---- P^T and (scale*dS)^T tiles
 #pragma unroll
       for (int f = 0; f < 4; ++f) {
-        g_short4 ppack, dpack;
+        short4v ppack, dpack;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float pv, dsv;
@@ -440,8 +368,8 @@ gqa_bwd_dkdv_kernel(const __hip_bfloat16* __restrict__ dout,
           dpack[r] = bf16_bits(dsv);
         }
         int jl = f * 16 + col_base;
-        *reinterpret_cast<g_short4a*>(pt + gswz(jl, i0g * 2, 128)) = ppack;
-        *reinterpret_cast<g_short4a*>(dst + gswz(jl, i0g * 2, 128)) = dpack;
+        tile_store(pt, jl, i0g, ppack);
+        tile_store(dst, jl, i0g, dpack);
       }
       __syncthreads();  // pt/dst complete across waves
 
@@ -449,13 +377,11 @@ gqa_bwd_dkdv_kernel(const __hip_bfloat16* __restrict__ dout,
 #pragma unroll
       for (int f = 0; f < D / 16; ++f) {
 #pragma unroll
-        for (int kk = 0; kk < GT; kk += 32) {
-          acck[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              gfrag(dst, strip, kk, lane, 128),
-              gfrag(qt, f * 16, kk, lane, 128), acck[f], 0, 0, 0);
-          accv[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              gfrag(pt, strip, kk, lane, 128),
-              gfrag(dot, f * 16, kk, lane, 128), accv[f], 0, 0, 0);
+        for (int kk = 0; kk < TILE; kk += 32) {
+          acck[f] = mfma_bf16(frag_load(dst, strip, kk, lane),
+                              frag_load(qt, f * 16, kk, lane), acck[f]);
+          accv[f] = mfma_bf16(frag_load(pt, strip, kk, lane),
+                              frag_load(dot, f * 16, kk, lane), accv[f]);
         }
       }
     }
@@ -494,22 +420,22 @@ gqa_bwd_dq_kernel(const __hip_bfloat16* __restrict__ dout,
   constexpr int RS = D * 2;
   const int b = blockIdx.x / Hq, h = blockIdx.x % Hq;
   const int hk = h / (Hq / Hkv);
-  const int q0 = blockIdx.y * GT;
+  const int q0 = blockIdx.y * TILE;
   const int off = Lk - Lq;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* qs = smem;              // [64][D]  Q rows (persistent)
-  char* dos = qs + GT * RS;     // [64][D]  dO rows (persistent)
-  char* ks = dos + GT * RS;     // [64][D]  K_t rows (per tile)
-  char* vs = ks + GT * RS;      // [64][D]  V_t rows (per tile)
-  char* kt = vs + GT * RS;      // [D][64]  K_t^T
-  char* dsn = kt + D * 128;     // [64 i][64 j]  scale*dS
+  char* qs = smem;                // [64][D]  Q rows (persistent)
+  char* dos = qs + TILE * RS;     // [64][D]  dO rows (persistent)
+  char* ks = dos + TILE * RS;     // [64][D]  K_t rows (per tile)
+  char* vs = ks + TILE * RS;      // [64][D]  V_t rows (per tile)
+  char* kt = vs + TILE * RS;      // [D][64]  K_t^T
+  char* dsn = kt + D * 128;       // [64 i][64 j]  scale*dS
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = tid >> 6;
-  const int col_base = lane & 15;
-  const int row_grp = (lane >> 4) << 2;
+  const int col_base = frag_col(lane);
+  const int row_grp = frag_row0(lane);
   const int strip = wid * 16;
 
   gstage<D, true, false>(q + (int64_t)b * q_sb + (int64_t)h * q_sh, q_sl, q0,
@@ -526,16 +452,16 @@ gqa_bwd_dq_kernel(const __hip_bfloat16* __restrict__ dout,
     dl_r[r] = i < Lq ? delta[rowb + i] : 0.f;
   }
 
-  g_float4 accq[D / 16];
+  float4v accq[D / 16];
 #pragma unroll
-  for (int f = 0; f < D / 16; ++f) accq[f] = g_float4{0, 0, 0, 0};
+  for (int f = 0; f < D / 16; ++f) accq[f] = float4v{0, 0, 0, 0};
 
   int kt_end = Lk;
-  if (causal) kt_end = min(Lk, q0 + GT + off);
+  if (causal) kt_end = min(Lk, q0 + TILE + off);
   const __hip_bfloat16* kb = k + (int64_t)b * k_sb + (int64_t)hk * k_sh;
   const __hip_bfloat16* vb = v + (int64_t)b * v_sb + (int64_t)hk * v_sh;
 
-  for (int kt0 = 0; kt0 < kt_end; kt0 += GT) {
+  for (int kt0 = 0; kt0 < kt_end; kt0 += TILE) {
     __syncthreads();  // previous tile's ks/vs/kt consumed
     gstage<D, true, true>(kb, k_sl, kt0, Lk, ks, kt, tid);
     gstage<D, true, false>(vb, v_sl, kt0, Lk, vs, nullptr, tid);
@@ -550,19 +476,17 @@ gqa_bwd_dq_kernel(const __hip_bfloat16* __restrict__ dout,
       if (jok[f] && key_pad) jok[f] = !key_pad[(int64_t)b * Lk + jcol[f]];
     }
 
-    g_float4 acc[4], accp[4];
+    float4v acc[4], accp[4];
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
-      acc[f] = g_float4{0, 0, 0, 0};
-      accp[f] = g_float4{0, 0, 0, 0};
+      acc[f] = float4v{0, 0, 0, 0};
+      accp[f] = float4v{0, 0, 0, 0};
 #pragma unroll
       for (int kk = 0; kk < D; kk += 32) {
-        acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            gfrag(qs, strip, kk, lane, RS), gfrag(ks, f * 16, kk, lane, RS),
-            acc[f], 0, 0, 0);
-        accp[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            gfrag(dos, strip, kk, lane, RS), gfrag(vs, f * 16, kk, lane, RS),
-            accp[f], 0, 0, 0);
+        acc[f] = mfma_bf16(frag_load(qs, strip, kk, lane, RS),
+                           frag_load(ks, f * 16, kk, lane, RS), acc[f]);
+        accp[f] = mfma_bf16(frag_load(dos, strip, kk, lane, RS),
+                            frag_load(vs, f * 16, kk, lane, RS), accp[f]);
       }
     }
 
@@ -574,9 +498,8 @@ gqa_bwd_dq_kernel(const __hip_bfloat16* __restrict__ dout,
         float pv, dsv;
         GQA_P_DS(f, r, pv, dsv);
         (void)pv;
-        int row = strip + row_grp + r;
-        *reinterpret_cast<g_short1a*>(
-            dsn + gswz(row, (f * 16 + col_base) * 2, 128)) = bf16_bits(dsv);
+        tile_store(dsn, strip + row_grp + r, f * 16 + col_base,
+                   bf16_bits(dsv));
       }
     }
     __builtin_amdgcn_wave_barrier();
@@ -585,10 +508,9 @@ gqa_bwd_dq_kernel(const __hip_bfloat16* __restrict__ dout,
 #pragma unroll
     for (int f = 0; f < D / 16; ++f) {
 #pragma unroll
-      for (int kk = 0; kk < GT; kk += 32) {
-        accq[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            gfrag(dsn, strip, kk, lane, 128),
-            gfrag(kt, f * 16, kk, lane, 128), accq[f], 0, 0, 0);
+      for (int kk = 0; kk < TILE; kk += 32) {
+        accq[f] = mfma_bf16(frag_load(dsn, strip, kk, lane),
+                            frag_load(kt, f * 16, kk, lane), accq[f]);
       }
     }
     __builtin_amdgcn_wave_barrier();
@@ -643,8 +565,8 @@ GqaShape gqa_check(const torch::Tensor& q, const torch::Tensor& k,
               ")");
   TORCH_CHECK(s.B >= 1 && s.Lq >= 1 && s.Lk >= 1,
               "gqa_attn: empty batch or sequence");
-  TORCH_CHECK((int64_t)(s.Lq + GT - 1) / GT <= 65535 &&
-                  (int64_t)(s.Lk + GT - 1) / GT <= 65535,
+  TORCH_CHECK((int64_t)(s.Lq + TILE - 1) / TILE <= 65535 &&
+                  (int64_t)(s.Lk + TILE - 1) / TILE <= 65535,
               "gqa_attn: sequence too long");
   if (key_pad.has_value()) {
     TORCH_CHECK(key_pad->is_cuda() &&
@@ -674,8 +596,8 @@ void gqa_launch_fwd(const GqaShape& s, const torch::Tensor& q,
                     const torch::Tensor& k, const torch::Tensor& v,
                     const bool* kp, torch::Tensor& out, torch::Tensor& lse,
                     float scale, bool causal) {
-  dim3 grid(s.B * s.Hq, (s.Lq + GT - 1) / GT);
-  size_t smem = 2 * GT * D * 2 + D * 128 + GT * 128;
+  dim3 grid(s.B * s.Hq, (s.Lq + TILE - 1) / TILE);
+  size_t smem = 2 * TILE * D * 2 + D * 128 + TILE * 128;
   static bool done[kMaxDev] = {};
   gqa_allow_lds(gqa_fwd_kernel<D>, smem, &done[q.get_device() % kMaxDev]);
   auto stream = at::cuda::getCurrentHIPStream();
@@ -722,8 +644,8 @@ void gqa_launch_bwd(const GqaShape& s, const torch::Tensor& dout,
     C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   {
-    dim3 grid(s.B * s.Hkv, (s.Lk + GT - 1) / GT);
-    size_t smem = 4 * GT * D * 2 + 2 * D * 128 + 2 * GT * 128;
+    dim3 grid(s.B * s.Hkv, (s.Lk + TILE - 1) / TILE);
+    size_t smem = 4 * TILE * D * 2 + 2 * D * 128 + 2 * TILE * 128;
     static bool done[kMaxDev] = {};
     gqa_allow_lds(gqa_bwd_dkdv_kernel<D>, smem, &done[dev]);
     hipLaunchKernelGGL(gqa_bwd_dkdv_kernel<D>, grid, dim3(256), smem, stream,
@@ -737,8 +659,8 @@ void gqa_launch_bwd(const GqaShape& s, const torch::Tensor& dout,
     C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   {
-    dim3 grid(s.B * s.Hq, (s.Lq + GT - 1) / GT);
-    size_t smem = 4 * GT * D * 2 + D * 128 + GT * 128;
+    dim3 grid(s.B * s.Hq, (s.Lq + TILE - 1) / TILE);
+    size_t smem = 4 * TILE * D * 2 + D * 128 + TILE * 128;
     static bool done[kMaxDev] = {};
     gqa_allow_lds(gqa_bwd_dq_kernel<D>, smem, &done[dev]);
     hipLaunchKernelGGL(gqa_bwd_dq_kernel<D>, grid, dim3(256), smem, stream,

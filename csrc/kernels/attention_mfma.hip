@@ -23,53 +23,11 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
-#include "../core/common.h"
+#include "../core/mfma_tile.h"
 
 namespace genrec {
 
 torch::Tensor colsum(torch::Tensor x);  // fused_elementwise.hip
-
-constexpr int TILE = 64;               // max Lq/Lk per block
-constexpr float NEG_BIG_MF = -1e9f;
-
-typedef __attribute__((ext_vector_type(8))) short short8v;
-typedef __attribute__((ext_vector_type(4))) float float4v;
-
-#define IDX4M(b, h, i, j, H, I, J) \
-  ((((int64_t)(b) * (H) + (h)) * (I) + (i)) * (J) + (j))
-
-// LDS tile: [64][64] bf16, row stride 128 B, XOR-swizzled byte offset.
-__device__ __forceinline__ int swz(int row, int byte_in_row) {
-  return row * 128 + (byte_in_row ^ ((row & 7) << 4));
-}
-
-
-// In-register 8x8 bf16 block transpose across the 8 lanes {8g+c : g=0..7}
-// (3 butterfly stages of shfl_xor; validated against a host simulation).
-// Turns a lane's natural row-chunk into a transposed row-chunk so the
-// LDS transpose staging becomes ONE b128 store instead of 8 scattered
-// u16 stores.
-__device__ __forceinline__ void xpose8x8(short (&vals)[8], int g) {
-#pragma unroll
-  for (int m = 1; m < 8; m <<= 1) {
-    short nv[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      int t = __shfl_xor((int)vals[e ^ m], 8 * m, 64);
-      nv[e] = ((e & m) != (g & m)) ? (short)t : vals[e];
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) vals[e] = nv[e];
-  }
-}
-
-// load one 16x32 A/B fragment (8 bf16 = 16 B per lane) from a swizzled tile
-__device__ __forceinline__ short8v frag_load(const char* base, int row0,
-                                             int k0, int lane) {
-  int row = row0 + (lane & 15);
-  int byte = (k0 + ((lane >> 4) << 3)) * 2;
-  return *reinterpret_cast<const short8v*>(base + swz(row, byte));
-}
 
 template <bool IS_SILU>
 __global__ void __launch_bounds__(256)
@@ -117,42 +75,19 @@ attn_fwd_mfma_kernel(
     int row = idx / (TILE / 8);
     int c8 = idx % (TILE / 8);        // 8-elem chunk
     int d0 = c8 * 8;
-    short8v z = {};
-    // Q tile
-    short8v val = z;
     int qi = q0 + row;
-    if (qi < Lq && d0 < D) {
-      val = *reinterpret_cast<const short8v*>(
-          &q[(int64_t)b * q_sb + h * q_sh + qi * q_sl + d0]);
-    }
-    *reinterpret_cast<short8v*>(qs + swz(row, d0 * 2)) = val;
-    // K tile
-    val = z;
-    if (row < Lk && d0 < D) {
-      val = *reinterpret_cast<const short8v*>(
-          &k[(int64_t)b * k_sb + h * k_sh + row * k_sl + d0]);
-    }
-    *reinterpret_cast<short8v*>(ks + swz(row, d0 * 2)) = val;
+    tile_store(qs, row, d0,
+               load8(q, (int64_t)b * q_sb + h * q_sh + qi * q_sl + d0,
+                     qi < Lq && d0 < D));
+    tile_store(ks, row, d0,
+               load8(k, (int64_t)b * k_sb + h * k_sh + row * k_sl + d0,
+                     row < Lk && d0 < D));
     // V^T tile: vt[d][j] = V[j][d]. Read V row-natural (ONE b128
     // coalesced load), transpose the 8x8 block in-register across the
     // lane group, store ONE b128 transposed row-chunk.
-    short8v vv = z;
-    if (row < Lk && d0 < D) {
-      vv = *reinterpret_cast<const short8v*>(
-          &v[(int64_t)b * v_sb + h * v_sh + row * v_sl + d0]);
-    }
-    {
-      const int g = (lane >> 3) & 7;
-      short tv[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) tv[e] = vv[e];
-      xpose8x8(tv, g);
-      short8v pack;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) pack[e] = tv[e];
-      // this lane now holds V[j0..j0+7][d0+g] -> vt row d0+g
-      *reinterpret_cast<short8v*>(vt + swz(d0 + g, (row & ~7) * 2)) = pack;
-    }
+    tile_store_tr(vt, row, d0, lane,
+                  load8(v, (int64_t)b * v_sb + h * v_sh + row * v_sl + d0,
+                        row < Lk && d0 < D));
   }
   __syncthreads();
 
@@ -167,13 +102,13 @@ attn_fwd_mfma_kernel(
     for (int kk = 0; kk < D; kk += 32) {
       short8v a = frag_load(qs, strip, kk, lane);
       short8v bfr = frag_load(ks, f * 16, kk, lane);
-      acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bfr, acc[f], 0, 0, 0);
+      acc[f] = mfma_bf16(a, bfr, acc[f]);
     }
   }
 
   // ---- epilogue on fragments: scale + bias + masks
-  const int col_base = lane & 15;
-  const int row_grp = (lane >> 4) << 2;  // rows row_grp..row_grp+3 (in strip)
+  const int col_base = frag_col(lane);
+  const int row_grp = frag_row0(lane);   // rows row_grp..row_grp+3 (in strip)
   float s_val[4][4];                     // [fragment][reg]
 #pragma unroll
   for (int f = 0; f < 4; ++f) {
@@ -187,15 +122,15 @@ attn_fwd_mfma_kernel(
         s *= scale;
         if (bias_dim) {
           int64_t bi = (bias_dim == 3) ? ((int64_t)h * Lq + i) * Lk + j
-                                       : IDX4M(b, h, i, j, H, Lq, Lk);
+                                       : idx4(b, h, i, j, H, Lq, Lk);
           s += bias_bf16 ? to_f32(bias_b[bi]) : bias_f[bi];
         } else if (bias_bucket) {
           // in-kernel rel-bias table gather (HSTU-style): no
           // materialized [H,Lq,Lk] bias tensor traffic
           s += bias_f[h * n_buckets + bias_bucket[(int64_t)i * Lk + j]];
         }
-        if (causal && j > i) s = NEG_BIG_MF;
-        if (key_pad && key_pad[(int64_t)b * Lk + j]) s = NEG_BIG_MF;
+        if (causal && j > i) s = NEG_BIG;
+        if (key_pad && key_pad[(int64_t)b * Lk + j]) s = NEG_BIG;
         if (add_mask) s += add_mask[(int64_t)i * Lk + j];
       } else {
         s = -INFINITY;
@@ -217,11 +152,8 @@ attn_fwd_mfma_kernel(
     // row softmax: combine 4 col fragments per reg, reduce over 16-lane grp
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      float m = fmaxf(fmaxf(s_val[0][r], s_val[1][r]),
-                      fmaxf(s_val[2][r], s_val[3][r]));
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1)
-        m = fmaxf(m, __shfl_xor(m, off, 64));
+      float m = grp16_max(fmaxf(fmaxf(s_val[0][r], s_val[1][r]),
+                                fmaxf(s_val[2][r], s_val[3][r])));
       float sum = 0.f;
 #pragma unroll
       for (int f = 0; f < 4; ++f) {
@@ -230,9 +162,7 @@ attn_fwd_mfma_kernel(
         p_val[f][r] = e;
         sum += e;
       }
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1)
-        sum += __shfl_xor(sum, off, 64);
+      sum = grp16_sum(sum);
       float inv = (sum > 0.f) ? 1.0f / sum : 0.f;
 #pragma unroll
       for (int f = 0; f < 4; ++f) p_val[f][r] *= inv;
@@ -248,10 +178,10 @@ attn_fwd_mfma_kernel(
       int j = f * 16 + col_base;
       float p = p_val[f][r];
       if (i < Lq && j < Lk) {
-        p_saved[IDX4M(b, h, i, j, H, Lq, Lk)] = IS_SILU ? s_val[f][r] : p;
+        p_saved[idx4(b, h, i, j, H, Lq, Lk)] = IS_SILU ? s_val[f][r] : p;
         if (query_mask) p *= query_mask[(int64_t)b * Lq + i];
         if (dropout_p > 0.f) {
-          unsigned long long gidx = IDX4M(b, h, i, j, H, Lq, Lk);
+          unsigned long long gidx = idx4(b, h, i, j, H, Lq, Lk);
           bool keep = (hash_rng(seed, gidx) & 0xFFFFFF) >=
                       (unsigned int)(dropout_p * 16777216.0f);
           drop_mask[gidx] = keep;
@@ -261,9 +191,7 @@ attn_fwd_mfma_kernel(
         p = 0.f;
       }
       // bf16 scatter into swizzled P tile (2 B per element)
-      int row = strip + row_grp + r;
-      *reinterpret_cast<__hip_bfloat16*>(ps + swz(row, j * 2)) =
-          __float2bfloat16(p);
+      tile_store(ps, strip + row_grp + r, j, bf16_bits(p));
     }
   }
   // wave-local: this wave only reads its own strip rows back
@@ -279,8 +207,7 @@ attn_fwd_mfma_kernel(
     for (int kk = 0; kk < TILE; kk += 32) {
       short8v a = frag_load(ps, strip, kk, lane);
       short8v bfr = frag_load(vt, f * 16, kk, lane);
-      acc2[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bfr, acc2[f],
-                                                        0, 0, 0);
+      acc2[f] = mfma_bf16(a, bfr, acc2[f]);
     }
   }
 #pragma unroll
@@ -368,50 +295,23 @@ attn_bwd_ds_kernel(
   for (int idx = tid; idx < TILE * (TILE / 8); idx += blockDim.x) {
     int row = idx / (TILE / 8);
     int d0 = (idx % (TILE / 8)) * 8;
-    short8v val = {};
-    if (row < Lq && d0 < D) {
-      val = *reinterpret_cast<const short8v*>(
-          &dout[(int64_t)b * do_sb + h * do_sh + row * do_sl + d0]);
-    }
-    *reinterpret_cast<short8v*>(dos + swz(row, d0 * 2)) = val;
-    short8v val2 = {};
-    if (row < Lk && d0 < D) {
-      val2 = *reinterpret_cast<const short8v*>(
-          &v[(int64_t)b * v_sb + h * v_sh + row * v_sl + d0]);
-    }
-    *reinterpret_cast<short8v*>(vs + swz(row, d0 * 2)) = val2;
+    const bool q_ok = row < Lq && d0 < D, k_ok = row < Lk && d0 < D;
+    short8v dd8 = load8(
+        dout, (int64_t)b * do_sb + h * do_sh + row * do_sl + d0, q_ok);
+    short8v vv8 = load8(
+        v, (int64_t)b * v_sb + h * v_sh + row * v_sl + d0, k_ok);
+    short8v kk8 = load8(
+        k, (int64_t)b * k_sb + h * k_sh + row * k_sl + d0, k_ok);
+    short8v qq8 = load8(
+        q, (int64_t)b * q_sb + h * q_sh + row * q_sl + d0, q_ok);
+    tile_store(dos, row, d0, dd8);
+    tile_store(vs, row, d0, vv8);
     // transposed images (row = d, cols = sequence positions): read each
     // source row-natural — ONE b128 coalesced load per tensor —
     // transpose 8x8 in-register, store ONE b128 per tensor.
-    short8v kk8 = {}, qq8 = {}, dd8 = {};
-    if (row < Lk && d0 < D) {
-      kk8 = *reinterpret_cast<const short8v*>(
-          &k[(int64_t)b * k_sb + h * k_sh + row * k_sl + d0]);
-    }
-    if (row < Lq && d0 < D) {
-      qq8 = *reinterpret_cast<const short8v*>(
-          &q[(int64_t)b * q_sb + h * q_sh + row * q_sl + d0]);
-      dd8 = *reinterpret_cast<const short8v*>(
-          &dout[(int64_t)b * do_sb + h * do_sh + row * do_sl + d0]);
-    }
-    {
-      const int g = (lane >> 3) & 7;
-      const int jb = (row & ~7) * 2;
-      short tk[8], tq2[8], td2[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        tk[e] = kk8[e]; tq2[e] = qq8[e]; td2[e] = dd8[e];
-      }
-      xpose8x8(tk, g);
-      xpose8x8(tq2, g);
-      xpose8x8(td2, g);
-      short8v pk, pq, pd;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { pk[e] = tk[e]; pq[e] = tq2[e]; pd[e] = td2[e]; }
-      *reinterpret_cast<short8v*>(kt + swz(d0 + g, jb)) = pk;
-      *reinterpret_cast<short8v*>(qt + swz(d0 + g, jb)) = pq;
-      *reinterpret_cast<short8v*>(dot + swz(d0 + g, jb)) = pd;
-    }
+    tile_store_tr(kt, row, d0, lane, kk8);
+    tile_store_tr(qt, row, d0, lane, qq8);
+    tile_store_tr(dot, row, d0, lane, dd8);
   }
   __syncthreads();
 
@@ -426,13 +326,12 @@ attn_bwd_ds_kernel(
     for (int kk = 0; kk < D; kk += 32) {
       short8v a = frag_load(dos, strip, kk, lane);
       short8v bfr = frag_load(vs, (fbase + fi) * 16, kk, lane);
-      acc[fi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bfr, acc[fi],
-                                                        0, 0, 0);
+      acc[fi] = mfma_bf16(a, bfr, acc[fi]);
     }
   }
 
-  const int col_base = lane & 15;
-  const int row_grp = (lane >> 4) << 2;
+  const int col_base = frag_col(lane);
+  const int row_grp = frag_row0(lane);
   float pv[2][4], da[2][4], ad[2][4];
 #pragma unroll
   for (int fi = 0; fi < 2; ++fi) {
@@ -441,12 +340,12 @@ attn_bwd_ds_kernel(
       int i = strip + row_grp + r;
       int j = (fbase + fi) * 16 + col_base;
       bool ok = (i < Lq) && (j < Lk);
-      float p = ok ? p_saved[IDX4M(b, h, i, j, H, Lq, Lk)] : 0.f;
+      float p = ok ? p_saved[idx4(b, h, i, j, H, Lq, Lk)] : 0.f;
       float m = 1.f;
       if (!IS_SILU && ok) {
         if (query_mask) m *= query_mask[(int64_t)b * Lq + i];
         if (dropout_p > 0.f) {
-          m *= drop_mask[IDX4M(b, h, i, j, H, Lq, Lk)] ? inv_keep : 0.f;
+          m *= drop_mask[idx4(b, h, i, j, H, Lq, Lk)] ? inv_keep : 0.f;
         }
       }
       pv[fi][r] = p;          // P (softmax) or S (silu)
@@ -470,14 +369,9 @@ attn_bwd_ds_kernel(
     // partial in-wave, publish to dotbuf[half], barrier, read the sum.
     float part[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float d0 = da[0][r] * pv[0][r] + da[1][r] * pv[1][r];
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1)
-        d0 += __shfl_xor(d0, off, 64);
-      part[r] = d0;
-    }
-    if ((lane & 15) == 0) {
+    for (int r = 0; r < 4; ++r)
+      part[r] = grp16_sum(da[0][r] * pv[0][r] + da[1][r] * pv[1][r]);
+    if (col_base == 0) {
 #pragma unroll
       for (int r = 0; r < 4; ++r)
         dotbuf[half * TILE + strip + row_grp + r] = part[r];
@@ -499,7 +393,6 @@ attn_bwd_ds_kernel(
   // (4x fewer LDS stores than per-element bf16 scatter -> fewer bank
   // conflict cycles; rocprofv3 SQ_LDS_BANK_CONFLICT was dominated by
   // these stores). Halves write disjoint j rows / column fragments.
-  typedef __attribute__((ext_vector_type(4))) short short4v;
   const int i0 = strip + row_grp;  // multiple of 4 -> byte i0*2 is 8B-aligned
 #pragma unroll
   for (int fi = 0; fi < 2; ++fi) {
@@ -510,13 +403,11 @@ attn_bwd_ds_kernel(
       int j = (fbase + fi) * 16 + col_base;
       float dval = (i < Lq && j < Lk) ? ds[fi][r] : 0.f;
       float aval = (i < Lq && j < Lk) ? ad[fi][r] : 0.f;
-      __hip_bfloat16 dh = __float2bfloat16(dval * scale);
-      __hip_bfloat16 ah = __float2bfloat16(aval);
-      dpack[r] = *reinterpret_cast<short*>(&dh);
-      apack[r] = *reinterpret_cast<short*>(&ah);
-      *reinterpret_cast<__hip_bfloat16*>(dsn + swz(i, j * 2)) = dh;
+      dpack[r] = bf16_bits(dval * scale);
+      apack[r] = bf16_bits(aval);
+      tile_store(dsn, i, j, dpack[r]);
       if (ds_saved && i < Lq && j < Lk) {
-        ds_saved[IDX4M(b, h, i, j, H, Lq, Lk)] = __float2bfloat16(dval);
+        ds_saved[idx4(b, h, i, j, H, Lq, Lk)] = __float2bfloat16(dval);
       }
       if (dtab_partial && i < Lq && j < Lk) {
         // LDS-privatized table-grad accumulation (32-entry histogram)
@@ -524,8 +415,8 @@ attn_bwd_ds_kernel(
       }
     }
     int j = (fbase + fi) * 16 + col_base;
-    *reinterpret_cast<short4v*>(dst + swz(j, i0 * 2)) = dpack;
-    *reinterpret_cast<short4v*>(adt + swz(j, i0 * 2)) = apack;
+    tile_store(dst, j, i0, dpack);
+    tile_store(adt, j, i0, apack);
   }
   // dQ's A-operand (dsn strip rows) now mixes both halves' column
   // fragments, and dK/dV read all pairs' dS^T/A_d^T columns: one
@@ -546,8 +437,7 @@ attn_bwd_ds_kernel(
       for (int kk = 0; kk < TILE; kk += 32) {
         short8v a = frag_load(dsn, strip, kk, lane);
         short8v bfr = frag_load(kt, (fbase + fi) * 16, kk, lane);
-        accq[fi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bfr, accq[fi],
-                                                           0, 0, 0);
+        accq[fi] = mfma_bf16(a, bfr, accq[fi]);
       }
     }
 #pragma unroll
@@ -574,12 +464,10 @@ attn_bwd_ds_kernel(
       for (int kk = 0; kk < TILE; kk += 32) {
         short8v a1 = frag_load(dst, strip, kk, lane);
         short8v b1 = frag_load(qt, (fbase + fi) * 16, kk, lane);
-        acck[fi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, acck[fi],
-                                                           0, 0, 0);
+        acck[fi] = mfma_bf16(a1, b1, acck[fi]);
         short8v a2 = frag_load(adt, strip, kk, lane);
         short8v b2 = frag_load(dot, (fbase + fi) * 16, kk, lane);
-        accv[fi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b2, accv[fi],
-                                                           0, 0, 0);
+        accv[fi] = mfma_bf16(a2, b2, accv[fi]);
       }
     }
 #pragma unroll

@@ -17,44 +17,9 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
-#include "../core/common.h"
+#include "../core/mfma_tile.h"
 
 namespace genrec {
-
-constexpr int HTILE = 64;
-constexpr float HNEG = -1e9f;
-
-typedef __attribute__((ext_vector_type(8))) short short8vh;
-typedef __attribute__((ext_vector_type(4))) float float4vh;
-
-#define HIDX4(b, h, i, j, H, I, J) \
-  ((((int64_t)(b) * (H) + (h)) * (I) + (i)) * (J) + (j))
-
-__device__ __forceinline__ int hswz(int row, int byte_in_row) {
-  return row * 128 + (byte_in_row ^ ((row & 7) << 4));
-}
-
-// 8x8 in-register block transpose (see attention_mfma.hip::xpose8x8)
-__device__ __forceinline__ void hxpose8x8(short (&vals)[8], int g) {
-#pragma unroll
-  for (int m = 1; m < 8; m <<= 1) {
-    short nv[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      int t = __shfl_xor((int)vals[e ^ m], 8 * m, 64);
-      nv[e] = ((e & m) != (g & m)) ? (short)t : vals[e];
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) vals[e] = nv[e];
-  }
-}
-
-__device__ __forceinline__ short8vh hfrag(const char* base, int row0, int k0,
-                                          int lane) {
-  int row = row0 + (lane & 15);
-  int byte = (k0 + ((lane >> 4) << 3)) * 2;
-  return *reinterpret_cast<const short8vh*>(base + hswz(row, byte));
-}
 
 __device__ __forceinline__ int time_bucket(long long ti, long long tj,
                                            int n_buckets) {
@@ -84,62 +49,38 @@ hstu_attn_fwd_kernel(
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* qs = smem;
-  char* ks = qs + HTILE * 128;
-  char* vt = ks + HTILE * 128;
-  char* ps = vt + HTILE * 128;
+  char* ks = qs + TILE * 128;
+  char* vt = ks + TILE * 128;
+  char* ps = vt + TILE * 128;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = tid >> 6;
 
-  for (int idx = tid; idx < HTILE * (HTILE / 8); idx += blockDim.x) {
-    int row = idx / (HTILE / 8);
-    int d0 = (idx % (HTILE / 8)) * 8;
-    short8vh val = {};
-    if (row < L && d0 < D) {
-      val = *reinterpret_cast<const short8vh*>(
-          &q[HIDX4(b, h, row, d0, H, L, D)]);
-    }
-    *reinterpret_cast<short8vh*>(qs + hswz(row, d0 * 2)) = val;
-    short8vh val2 = {};
-    if (row < L && d0 < D) {
-      val2 = *reinterpret_cast<const short8vh*>(
-          &k[HIDX4(b, h, row, d0, H, L, D)]);
-    }
-    *reinterpret_cast<short8vh*>(ks + hswz(row, d0 * 2)) = val2;
+  for (int idx = tid; idx < TILE * (TILE / 8); idx += blockDim.x) {
+    int row = idx / (TILE / 8);
+    int d0 = (idx % (TILE / 8)) * 8;
+    const bool ok = row < L && d0 < D;
+    const int64_t src = idx4(b, h, row, d0, H, L, D);
+    tile_store(qs, row, d0, load8(q, src, ok));
+    tile_store(ks, row, d0, load8(k, src, ok));
     // V^T: coalesced natural-row load + in-register 8x8 transpose
-    short8vh vv = {};
-    if (row < L && d0 < D) {
-      vv = *reinterpret_cast<const short8vh*>(
-          &v[HIDX4(b, h, row, d0, H, L, D)]);
-    }
-    {
-      const int g = (lane >> 3) & 7;
-      short tv[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) tv[e] = vv[e];
-      hxpose8x8(tv, g);
-      short8vh pack;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) pack[e] = tv[e];
-      *reinterpret_cast<short8vh*>(vt + hswz(d0 + g, (row & ~7) * 2)) = pack;
-    }
+    tile_store_tr(vt, row, d0, lane, load8(v, src, ok));
   }
   __syncthreads();
 
   const int strip = wid * 16;
-  float4vh acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+  float4v acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
 #pragma unroll
   for (int f = 0; f < 4; ++f) {
     for (int kk = 0; kk < D; kk += 32) {
-      acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-          hfrag(qs, strip, kk, lane), hfrag(ks, f * 16, kk, lane), acc[f],
-          0, 0, 0);
+      acc[f] = mfma_bf16(frag_load(qs, strip, kk, lane),
+                         frag_load(ks, f * 16, kk, lane), acc[f]);
     }
   }
 
-  const int col_base = lane & 15;
-  const int row_grp = (lane >> 4) << 2;
+  const int col_base = frag_col(lane);
+  const int row_grp = frag_row0(lane);
 #pragma unroll
   for (int f = 0; f < 4; ++f) {
 #pragma unroll
@@ -155,26 +96,24 @@ hstu_attn_fwd_kernel(
                                ts[(int64_t)b * L + j], n_time);
           s += to_f32(time_table[(int64_t)tb * H + h]);
         }
-        if (j > i) s = HNEG;                                     // causal
-        if (key_pad && key_pad[(int64_t)b * L + j]) s = HNEG;    // pad
-        s_saved[HIDX4(b, h, i, j, H, L, L)] = s;
+        if (j > i) s = NEG_BIG;                                     // causal
+        if (key_pad && key_pad[(int64_t)b * L + j]) s = NEG_BIG;    // pad
+        s_saved[idx4(b, h, i, j, H, L, L)] = s;
         p = s * sigmoidf_dev(s);
       }
-      *reinterpret_cast<__hip_bfloat16*>(ps + hswz(i, j * 2)) =
-          __float2bfloat16(p);
+      tile_store(ps, i, j, bf16_bits(p));
     }
   }
   __builtin_amdgcn_wave_barrier();
 
-  float4vh acc2[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+  float4v acc2[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
   const int nfrag_d = (D + 15) / 16;
 #pragma unroll
   for (int f = 0; f < 4; ++f) {
     if (f >= nfrag_d) break;
-    for (int kk = 0; kk < HTILE; kk += 32) {
-      acc2[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-          hfrag(ps, strip, kk, lane), hfrag(vt, f * 16, kk, lane), acc2[f],
-          0, 0, 0);
+    for (int kk = 0; kk < TILE; kk += 32) {
+      acc2[f] = mfma_bf16(frag_load(ps, strip, kk, lane),
+                          frag_load(vt, f * 16, kk, lane), acc2[f]);
     }
   }
 #pragma unroll
@@ -185,7 +124,7 @@ hstu_attn_fwd_kernel(
       int i = strip + row_grp + r;
       int d = f * 16 + col_base;
       if (i < L && d < D) {
-        out[HIDX4(b, h, i, d, H, L, D)] = __float2bfloat16(acc2[f][r]);
+        out[idx4(b, h, i, d, H, L, D)] = __float2bfloat16(acc2[f][r]);
       }
     }
   }
@@ -212,14 +151,14 @@ hstu_attn_bwd_kernel(
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* dos = smem;
-  char* vs = dos + HTILE * 128;
-  char* kt = vs + HTILE * 128;
-  char* qt = kt + HTILE * 128;
-  char* dot = qt + HTILE * 128;
-  char* dsn = dot + HTILE * 128;
-  char* dst = dsn + HTILE * 128;
-  char* adt = dst + HTILE * 128;
-  float* hist = reinterpret_cast<float*>(adt + HTILE * 128);  // [n_pos+n_time]
+  char* vs = dos + TILE * 128;
+  char* kt = vs + TILE * 128;
+  char* qt = kt + TILE * 128;
+  char* dot = qt + TILE * 128;
+  char* dsn = dot + TILE * 128;
+  char* dst = dsn + TILE * 128;
+  char* adt = dst + TILE * 128;
+  float* hist = reinterpret_cast<float*>(adt + TILE * 128);  // [n_pos+n_time]
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -227,80 +166,50 @@ hstu_attn_bwd_kernel(
   const int n_hist = n_pos + n_time;
   for (int i = tid; i < n_hist; i += blockDim.x) hist[i] = 0.f;
 
-  for (int idx = tid; idx < HTILE * (HTILE / 8); idx += blockDim.x) {
-    int row = idx / (HTILE / 8);
-    int d0 = (idx % (HTILE / 8)) * 8;
-    short8vh val = {};
-    if (row < L && d0 < D) {
-      val = *reinterpret_cast<const short8vh*>(
-          &dout[HIDX4(b, h, row, d0, H, L, D)]);
-    }
-    *reinterpret_cast<short8vh*>(dos + hswz(row, d0 * 2)) = val;
-    short8vh val2 = {};
-    if (row < L && d0 < D) {
-      val2 = *reinterpret_cast<const short8vh*>(
-          &v[HIDX4(b, h, row, d0, H, L, D)]);
-    }
-    *reinterpret_cast<short8vh*>(vs + hswz(row, d0 * 2)) = val2;
+  for (int idx = tid; idx < TILE * (TILE / 8); idx += blockDim.x) {
+    int row = idx / (TILE / 8);
+    int d0 = (idx % (TILE / 8)) * 8;
+    const bool ok = row < L && d0 < D;
+    const int64_t src = idx4(b, h, row, d0, H, L, D);
+    short8v dd8 = load8(dout, src, ok);
+    short8v vv8 = load8(v, src, ok);
+    short8v kk8 = load8(k, src, ok);
+    short8v qq8 = load8(q, src, ok);
+    tile_store(dos, row, d0, dd8);
+    tile_store(vs, row, d0, vv8);
     // K^T/Q^T/dO^T: coalesced natural-row b128 loads + in-register 8x8
     // transpose, one b128 LDS store per tensor
-    short8vh kk8 = {}, qq8 = {}, dd8 = {};
-    if (row < L && d0 < D) {
-      kk8 = *reinterpret_cast<const short8vh*>(
-          &k[HIDX4(b, h, row, d0, H, L, D)]);
-      qq8 = *reinterpret_cast<const short8vh*>(
-          &q[HIDX4(b, h, row, d0, H, L, D)]);
-      dd8 = *reinterpret_cast<const short8vh*>(
-          &dout[HIDX4(b, h, row, d0, H, L, D)]);
-    }
-    {
-      const int g = (lane >> 3) & 7;
-      const int jb = (row & ~7) * 2;
-      short tk[8], tq2[8], td2[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        tk[e] = kk8[e]; tq2[e] = qq8[e]; td2[e] = dd8[e];
-      }
-      hxpose8x8(tk, g);
-      hxpose8x8(tq2, g);
-      hxpose8x8(td2, g);
-      short8vh pk, pq, pd;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { pk[e] = tk[e]; pq[e] = tq2[e]; pd[e] = td2[e]; }
-      *reinterpret_cast<short8vh*>(kt + hswz(d0 + g, jb)) = pk;
-      *reinterpret_cast<short8vh*>(qt + hswz(d0 + g, jb)) = pq;
-      *reinterpret_cast<short8vh*>(dot + hswz(d0 + g, jb)) = pd;
-    }
+    tile_store_tr(kt, row, d0, lane, kk8);
+    tile_store_tr(qt, row, d0, lane, qq8);
+    tile_store_tr(dot, row, d0, lane, dd8);
   }
   __syncthreads();
 
   const int strip = wid * 16;
-  float4vh acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+  float4v acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
 #pragma unroll
   for (int f = 0; f < 4; ++f) {
     for (int kk = 0; kk < D; kk += 32) {
-      acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-          hfrag(dos, strip, kk, lane), hfrag(vs, f * 16, kk, lane), acc[f],
-          0, 0, 0);
+      acc[f] = mfma_bf16(frag_load(dos, strip, kk, lane),
+                         frag_load(vs, f * 16, kk, lane), acc[f]);
     }
   }
 
-  const int col_base = lane & 15;
-  const int row_grp = (lane >> 4) << 2;
+  const int col_base = frag_col(lane);
+  const int row_grp = frag_row0(lane);
   // transposed-tile stores pack a lane's 4 r-values (consecutive columns
   // of row j) into ONE aligned 8-byte ds_write — see attention_mfma.hip
-  typedef __attribute__((ext_vector_type(4))) short short4vh;
   const int i0 = strip + row_grp;
 #pragma unroll
   for (int f = 0; f < 4; ++f) {
-    short4vh dpack, apack;
+    short4v dpack, apack;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       int i = i0 + r;
       int j = f * 16 + col_base;
       float dsv = 0.f, adv = 0.f;
       if (i < L && j < L) {
-        float s = s_saved[HIDX4(b, h, i, j, H, L, L)];
+        float s = s_saved[idx4(b, h, i, j, H, L, L)];
         float sg = sigmoidf_dev(s);
         dsv = acc[f][r] * sg * (1.f + s * (1.f - sg));
         adv = s * sg;  // A = silu(S)
@@ -315,28 +224,25 @@ hstu_attn_bwd_kernel(
           }
         }
       }
-      __hip_bfloat16 dh = __float2bfloat16(dsv);
-      __hip_bfloat16 ah = __float2bfloat16(adv);
-      dpack[r] = *reinterpret_cast<short*>(&dh);
-      apack[r] = *reinterpret_cast<short*>(&ah);
-      *reinterpret_cast<__hip_bfloat16*>(dsn + hswz(i, j * 2)) = dh;
+      dpack[r] = bf16_bits(dsv);
+      apack[r] = bf16_bits(adv);
+      tile_store(dsn, i, j, dpack[r]);
     }
     int j = f * 16 + col_base;
-    *reinterpret_cast<short4vh*>(dst + hswz(j, i0 * 2)) = dpack;
-    *reinterpret_cast<short4vh*>(adt + hswz(j, i0 * 2)) = apack;
+    tile_store(dst, j, i0, dpack);
+    tile_store(adt, j, i0, apack);
   }
   __builtin_amdgcn_wave_barrier();
 
   const int nfrag_d = (D + 15) / 16;
   {  // dQ
-    float4vh a4[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    float4v a4[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
       if (f >= nfrag_d) break;
-      for (int kk = 0; kk < HTILE; kk += 32) {
-        a4[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            hfrag(dsn, strip, kk, lane), hfrag(kt, f * 16, kk, lane), a4[f],
-            0, 0, 0);
+      for (int kk = 0; kk < TILE; kk += 32) {
+        a4[f] = mfma_bf16(frag_load(dsn, strip, kk, lane),
+                          frag_load(kt, f * 16, kk, lane), a4[f]);
       }
     }
 #pragma unroll
@@ -347,7 +253,7 @@ hstu_attn_bwd_kernel(
         int i = strip + row_grp + r;
         int d = f * 16 + col_base;
         if (i < L && d < D) {
-          dq_out[HIDX4(b, h, i, d, H, L, D)] = __float2bfloat16(a4[f][r]);
+          dq_out[idx4(b, h, i, d, H, L, D)] = __float2bfloat16(a4[f][r]);
         }
       }
     }
@@ -355,18 +261,16 @@ hstu_attn_bwd_kernel(
   __syncthreads();
 
   {  // dK, dV
-    float4vh ak[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-    float4vh av[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    float4v ak[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    float4v av[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
       if (f >= nfrag_d) break;
-      for (int kk = 0; kk < HTILE; kk += 32) {
-        ak[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            hfrag(dst, strip, kk, lane), hfrag(qt, f * 16, kk, lane), ak[f],
-            0, 0, 0);
-        av[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            hfrag(adt, strip, kk, lane), hfrag(dot, f * 16, kk, lane), av[f],
-            0, 0, 0);
+      for (int kk = 0; kk < TILE; kk += 32) {
+        ak[f] = mfma_bf16(frag_load(dst, strip, kk, lane),
+                          frag_load(qt, f * 16, kk, lane), ak[f]);
+        av[f] = mfma_bf16(frag_load(adt, strip, kk, lane),
+                          frag_load(dot, f * 16, kk, lane), av[f]);
       }
     }
 #pragma unroll
@@ -377,8 +281,8 @@ hstu_attn_bwd_kernel(
         int j = strip + row_grp + r;
         int d = f * 16 + col_base;
         if (j < L && d < D) {
-          dk_out[HIDX4(b, h, j, d, H, L, D)] = __float2bfloat16(ak[f][r]);
-          dv_out[HIDX4(b, h, j, d, H, L, D)] = __float2bfloat16(av[f][r]);
+          dk_out[idx4(b, h, j, d, H, L, D)] = __float2bfloat16(ak[f][r]);
+          dv_out[idx4(b, h, j, d, H, L, D)] = __float2bfloat16(av[f][r]);
         }
       }
     }
@@ -405,7 +309,7 @@ std::vector<torch::Tensor> hstu_attn_fwd(
     c10::optional<torch::Tensor> key_pad) {
   TORCH_CHECK(q.scalar_type() == torch::kBFloat16 && q.dim() == 4);
   const int B = q.size(0), H = q.size(1), L = q.size(2), D = q.size(3);
-  TORCH_CHECK(L <= HTILE && D % 32 == 0 && D <= HTILE);
+  TORCH_CHECK(L <= TILE && D % 32 == 0 && D <= TILE);
   TORCH_CHECK(pos_table.scalar_type() == torch::kBFloat16);
   auto out = torch::empty_like(q);
   auto s_saved = torch::empty({B, H, L, L},
@@ -417,7 +321,7 @@ std::vector<torch::Tensor> hstu_attn_fwd(
   int n_time = time_table.has_value() ? time_table->size(0) : 0;
   dim3 block(256);
   dim3 grid(B * H);
-  size_t smem = 4 * HTILE * 128;
+  size_t smem = 4 * TILE * 128;
   auto stream = at::cuda::getCurrentHIPStream();
   hipLaunchKernelGGL((hstu_attn_fwd_kernel<__hip_bfloat16>), grid, block,
       smem, stream,
@@ -463,7 +367,7 @@ std::vector<torch::Tensor> hstu_attn_bwd(
   auto dc = dout.contiguous();
   dim3 block(256);
   dim3 grid(B * H);
-  size_t smem = 8 * HTILE * 128 +
+  size_t smem = 8 * TILE * 128 +
                 ((size_t)n_pos + (size_t)n_time) * sizeof(float);
   auto stream = at::cuda::getCurrentHIPStream();
   hipLaunchKernelGGL((hstu_attn_bwd_kernel<__hip_bfloat16>), grid, block,

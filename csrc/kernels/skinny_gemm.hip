@@ -21,7 +21,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
-#include "../core/common.h"
+#include "../core/mfma_tile.h"
 
 namespace genrec {
 
@@ -30,37 +30,6 @@ namespace {
 constexpr int BM = 64;    // M rows per workgroup
 constexpr int BN = 384;   // N cols per workgroup (96 per wave)
 constexpr int BK = 64;    // K slice per stage
-
-typedef __attribute__((ext_vector_type(8))) short short8v;
-typedef __attribute__((ext_vector_type(4))) float float4v;
-
-// 128-byte LDS rows with the T2 XOR swizzle (same as attention tiles)
-__device__ __forceinline__ int swz128(int row, int byte_in_row) {
-  return row * 128 + (byte_in_row ^ ((row & 7) << 4));
-}
-
-__device__ __forceinline__ short8v ld_frag(const char* base, int row0,
-                                           int k0, int lane) {
-  int row = row0 + (lane & 15);
-  int byte = (k0 + ((lane >> 4) << 3)) * 2;
-  return *reinterpret_cast<const short8v*>(base + swz128(row, byte));
-}
-
-// In-register 8x8 bf16 block transpose across the 8-lane group (same
-// butterfly as attention_mfma.hip's V^T staging).
-__device__ __forceinline__ void xpose8x8g(short (&vals)[8], int g) {
-#pragma unroll
-  for (int m = 1; m < 8; m <<= 1) {
-    short nv[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      int t = __shfl_xor((int)vals[e ^ m], 8 * m, 64);
-      nv[e] = ((e & m) != (g & m)) ? (short)t : vals[e];
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) vals[e] = nv[e];
-  }
-}
 
 // TRANS_B=false: y[M,N] = x[M,K] @ w[N,K]^T  (linear forward; w row-major
 //                in K — B image rows are w rows, staged directly)
@@ -102,62 +71,38 @@ skinny_gemm_kernel(const __hip_bfloat16* __restrict__ x,  // [M,K]
   const int a_row = tid >> 3;              // A chunk coords (x2, +32 rows)
   const int a_c8 = (tid & 7) * 8;
   short8v a_reg[2], w_reg[12];
-  const int g = (lane >> 3) & 7;           // TN transpose group
   const int t_row = ((lane & 7) << 3) | (lane >> 3);  // TN source k-row
 
   auto load_regs = [&](int k0) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       int mi = m0 + a_row + i * 32;
-      a_reg[i] = short8v{};
-      if (mi < M) {
-        a_reg[i] = *reinterpret_cast<const short8v*>(
-            &x[(int64_t)mi * K + k0 + a_c8]);
-      }
+      a_reg[i] = load8(x, (int64_t)mi * K + k0 + a_c8, mi < M);
     }
 #pragma unroll
     for (int j = 0; j < 12; ++j) {
-      w_reg[j] = short8v{};
       if (!TRANS_B) {
         int ni = n0 + a_row + j * 32;      // same row/chunk walk as A
-        if (ni < N) {
-          w_reg[j] = *reinterpret_cast<const short8v*>(
-              &w[(int64_t)ni * K + k0 + a_c8]);
-        }
+        w_reg[j] = load8(w, (int64_t)ni * K + k0 + a_c8, ni < N);
       } else {
         int jn = wid + j * 4;              // n chunk (8 cols)
         int ki = k0 + t_row;
         int nj = n0 + 8 * jn;
-        if (ki < K && nj < N) {
-          w_reg[j] = *reinterpret_cast<const short8v*>(
-              &w[(int64_t)ki * N + nj]);
-        }
+        w_reg[j] = load8(w, (int64_t)ki * N + nj, ki < K && nj < N);
       }
     }
   };
 
   auto write_lds = [&]() {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      *reinterpret_cast<short8v*>(
-          xs + swz128(a_row + i * 32, a_c8 * 2)) = a_reg[i];
-    }
+    for (int i = 0; i < 2; ++i) tile_store(xs, a_row + i * 32, a_c8, a_reg[i]);
 #pragma unroll
     for (int j = 0; j < 12; ++j) {
       if (!TRANS_B) {
-        *reinterpret_cast<short8v*>(
-            ws + swz128(a_row + j * 32, a_c8 * 2)) = w_reg[j];
+        tile_store(ws, a_row + j * 32, a_c8, w_reg[j]);
       } else {
-        short tv[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) tv[e] = w_reg[j][e];
-        xpose8x8g(tv, g);
-        short8v pack;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) pack[e] = tv[e];
-        int jn = wid + j * 4;
-        *reinterpret_cast<short8v*>(
-            ws + swz128(8 * jn + g, ((t_row & ~7) * 2))) = pack;
+        // source k-row t_row, n-chunk jn -> image row 8*jn + g
+        tile_store_tr(ws, t_row, 8 * (wid + j * 4), lane, w_reg[j]);
       }
     }
   };
@@ -167,14 +112,13 @@ skinny_gemm_kernel(const __hip_bfloat16* __restrict__ x,  // [M,K]
     for (int kk = 0; kk < BK; kk += 32) {
       short8v a[4];
 #pragma unroll
-      for (int mf = 0; mf < 4; ++mf) a[mf] = ld_frag(xs, mf * 16, kk, lane);
+      for (int mf = 0; mf < 4; ++mf) a[mf] = frag_load(xs, mf * 16, kk, lane);
 #pragma unroll
       for (int nf = 0; nf < 6; ++nf) {
-        short8v b = ld_frag(ws, nw0 + nf * 16, kk, lane);
+        short8v b = frag_load(ws, nw0 + nf * 16, kk, lane);
 #pragma unroll
         for (int mf = 0; mf < 4; ++mf) {
-          acc[nf][mf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              a[mf], b, acc[nf][mf], 0, 0, 0);
+          acc[nf][mf] = mfma_bf16(a[mf], b, acc[nf][mf]);
         }
       }
     }
@@ -195,8 +139,8 @@ skinny_gemm_kernel(const __hip_bfloat16* __restrict__ x,  // [M,K]
   }
 
   // epilogue: C layout row=(lane>>4)*4+r (within m-frag), col=lane&15
-  const int col_base = lane & 15;
-  const int row_grp = (lane >> 4) << 2;
+  const int col_base = frag_col(lane);
+  const int row_grp = frag_row0(lane);
 #pragma unroll
   for (int nf = 0; nf < 6; ++nf) {
     int n = n0 + nw0 + nf * 16 + col_base;

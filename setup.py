@@ -40,6 +40,15 @@ if os.environ.get("GENREC_DEBUG_BUILD", "0") == "1":
     cxx_flags = ["-O1", "-g", "-std=c++17", "-fno-omit-frame-pointer"]
     hip_flags = ["-O1", "-g", "-std=c++17", "-fno-omit-frame-pointer"]
 
+# The generated HIP compile rule tracks no header dependencies, so an edit
+# to a shared header (csrc/core/*.h holds the MFMA tile primitives of five
+# kernels) would leave stale objects. Put the headers' newest mtime on the
+# HIP command line: ninja rebuilds an object whose command changed.
+import glob
+
+hip_flags.append("-DGENREC_CORE_HEADERS_MTIME=%d" % max(
+    os.stat(h).st_mtime_ns for h in glob.glob(os.path.join(ROOT, "csrc/core/*.h"))))
+
 from setuptools import find_packages
 
 setup(

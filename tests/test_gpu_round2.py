@@ -310,7 +310,8 @@ def test_rccl_two_ranks_two_gpus():
 
 @pytest.mark.parametrize("shape", [(15616, 384, 384), (15616, 768, 384),
                                    (15616, 1024, 384), (15616, 384, 1024),
-                                   (6400, 256, 64), (1000, 400, 128)])
+                                   (6400, 256, 64), (1000, 400, 128),
+                                   (77, 400, 64)])
 def test_skinny_gemm_matches_matmul(shape):
     """Hand tall-skinny MFMA GEMM vs hipBLASLt (same bf16 inputs)."""
     from genrec_amd import ops
@@ -331,7 +332,7 @@ def test_skinny_gemm_matches_matmul(shape):
 
 
 @pytest.mark.parametrize("shape", [(15616, 384, 384), (15616, 384, 1024),
-                                   (1000, 384, 128)])
+                                   (1000, 384, 128), (77, 64, 136)])
 def test_skinny_gemm_tn_matches_matmul(shape):
     """Transposed-B variant (dX backward): y = x @ w with w [K,N]."""
     from genrec_amd import ops

@@ -344,15 +344,15 @@ def test_embedding_fwd_bwd():
         (w3.grad - w4.grad).abs().max()
 
 
-@pytest.mark.parametrize("case", ["plain", "sasrec", "t5_bias", "t5_addmask",
-                                  "hstu_silu", "dropout"])
+@pytest.mark.parametrize("case", ["plain", "plain_d32", "sasrec", "t5_bias",
+                                  "t5_addmask", "hstu_silu", "dropout"])
 def test_mfma_attention_vs_eager(case):
     """bf16 MFMA path vs fp32 eager reference (fwd + bwd)."""
     from genrec_amd.ops import eager
     from genrec_amd.ops.attention import fused_attention
 
     torch.manual_seed(7)
-    B, H, L, D = 3, 2, 61, 64
+    B, H, L, D = 3, 2, 61, (32 if case == "plain_d32" else 64)
     q = torch.randn(B, H, L, D, device=DEV, dtype=torch.bfloat16,
                     requires_grad=True)
     k = torch.randn_like(q, requires_grad=True)
@@ -770,18 +770,18 @@ def test_mfma_attention_strided_views_match_contiguous():
 
 
 @pytest.mark.parametrize("case", ["plain128", "bias80", "causal128",
-                                  "padmask96", "dropout128"])
+                                  "padmask96", "dropout128", "plain130_d32"])
 def test_flash_attention_vs_eager(case):
     """Flash-tiled kernels (Lk>64) vs the eager fp32 reference. Default
     dispatch path for Lk>64 since round 2."""
     from genrec_amd.ops.attention import fused_attention
 
     torch.manual_seed(0)
-    B, H, D = 4, 3, 64
+    B, H, D = 4, 3, (32 if case == "plain130_d32" else 64)
     Lq = {"plain128": 100, "bias80": 80, "causal128": 128,
-          "padmask96": 61, "dropout128": 90}[case]
+          "padmask96": 61, "dropout128": 90, "plain130_d32": 70}[case]
     Lk = {"plain128": 128, "bias80": 80, "causal128": 128,
-          "padmask96": 96, "dropout128": 128}[case]
+          "padmask96": 96, "dropout128": 128, "plain130_d32": 130}[case]
     q = torch.randn(B, H, Lq, D, device=DEV, dtype=torch.bfloat16,
                     requires_grad=True)
     k = torch.randn(B, H, Lk, D, device=DEV, dtype=torch.bfloat16,
