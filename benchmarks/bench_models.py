@@ -36,15 +36,18 @@ def _timeit(step, steps, warmup, device):
     return time.perf_counter() - t0
 
 
-def _graph_step(model, batch, loss_getter, device, betas=(0.9, 0.999)):
+def _graph_step(model, batch, loss_getter, device, betas=(0.9, 0.999),
+                use_graph=True):
     """hipGraph-captured full step on CUDA (the trainers' production
-    path); eager AdamW fallback elsewhere."""
+    path); eager AdamW fallback elsewhere. use_graph=False keeps the fused
+    flat AdamW but launches the step eagerly."""
     if device.type == "cuda":
         from genrec_amd.parallel.graph_runner import GraphedTrainStep
 
         runner = GraphedTrainStep(model, batch, loss_getter, lr=1e-3,
                                   betas=betas, weight_decay=0.0,
-                                  clip_norm=None, world=1, use_graph=True)
+                                  clip_norm=None, world=1,
+                                  use_graph=use_graph)
         return lambda i: runner.step(batch)
     opt = torch.optim.AdamW(model.parameters(), lr=1e-3, betas=betas)
 
@@ -129,10 +132,19 @@ def bench_rqvae(device, steps, warmup):
                 ms_per_step=el / steps * 1e3)
 
 
-def bench_lcrec(device, steps, warmup, full_size=False, attn_impl="sdpa"):
+def bench_lcrec(device, steps, warmup, full_size=False, attn_impl="sdpa",
+                loss_impl="hf", vocab=None, response_tokens=None,
+                eager_step=False):
     """LCRec SFT step: Qwen2-1.5B-shaped backbone (lcrec/amazon/lcrec.gin:
     B=32, L=512, bf16, grad ckpt) — full size only on GPU. attn_impl selects
-    the backbone attention ("sdpa" | "genrec_gqa") for same-box A/Bs."""
+    the backbone attention ("sdpa" | "genrec_gqa") and loss_impl the loss
+    ("hf" = the backbone's own | "genrec_lce") for same-box A/Bs. `vocab`
+    widens the head to a real tokenizer's size (the offline tokenizer is
+    tiny); `response_tokens` supervises only the last K positions of each
+    sample, as sft_collate does (default: every position, as before).
+    `eager_step` launches the step without hipGraph capture, as
+    lcrec_trainer does; only then can "genrec_lce" drop the unsupervised
+    rows (the compaction needs one host sync)."""
     from genrec_amd.models.lcrec import LCRec, default_qwen_config
 
     torch.manual_seed(0)
@@ -140,8 +152,16 @@ def bench_lcrec(device, steps, warmup, full_size=False, attn_impl="sdpa"):
     cfg = default_qwen_config() if full_size else default_qwen_config(
         vocab_size=2048, hidden_size=256, num_layers=4, num_heads=8,
         num_kv_heads=2, intermediate_size=512)
-    model = LCRec(config=cfg, attn_implementation=attn_impl)
+    if vocab is not None:
+        cfg.vocab_size = vocab
+    model = LCRec(config=cfg, attn_implementation=attn_impl,
+                  loss_implementation=None if loss_impl == "hf"
+                  else loss_impl)
     model.add_codebook_tokens(5, 256)
+    if vocab is not None:
+        # add_codebook_tokens resized to the offline tokenizer's length
+        model.model.resize_token_embeddings(vocab + 5 * 256)
+        model.model.config.vocab_size = vocab + 5 * 256
     if full_size:
         model.gradient_checkpointing_enable()
     model = model.to(device)
@@ -150,13 +170,18 @@ def bench_lcrec(device, steps, warmup, full_size=False, attn_impl="sdpa"):
     V = model.model.config.vocab_size
     ids = torch.randint(0, V, (B, L), device=device)
     attn = torch.ones_like(ids)
+    labels = ids
+    if response_tokens is not None:
+        labels = ids.clone()
+        labels[:, :L - response_tokens] = -100
     model.train()
     # GraphedTrainStep: fused flat AdamW + steal-grads even when hipGraph
     # capture falls back to eager (HF checkpointing is not capture-safe)
     step = _graph_step(model,
                        {"input_ids": ids, "attention_mask": attn,
-                        "labels": ids},
-                       lambda out: out.loss, device)
+                        "labels": labels},
+                       lambda out: out.loss, device,
+                       use_graph=not eager_step)
 
     if device.type == "cuda":
         torch.cuda.reset_peak_memory_stats(device)
@@ -164,7 +189,10 @@ def bench_lcrec(device, steps, warmup, full_size=False, attn_impl="sdpa"):
     peak = torch.cuda.max_memory_allocated(device) / 2**30 \
         if device.type == "cuda" else None
     return dict(model="lcrec-qwen2-1.5b" if full_size else "lcrec-tiny",
-                attn=attn_impl, batch=B, seq_len=L, samples_per_s=B * steps / el,
+                attn=attn_impl, loss=loss_impl, vocab=V,
+                step="eager" if eager_step else "graph",
+                supervised_per_sample=response_tokens or L,
+                batch=B, seq_len=L, samples_per_s=B * steps / el,
                 tokens_per_s=B * L * steps / el,
                 ms_per_step=el / steps * 1e3, peak_hbm_gib=peak)
 
@@ -208,6 +236,15 @@ def main():
     p.add_argument("--lcrec-full", action="store_true")
     p.add_argument("--lcrec-attn", choices=["sdpa", "genrec_gqa"],
                    default="sdpa")
+    p.add_argument("--lcrec-loss", choices=["hf", "genrec_lce"],
+                   default="hf")
+    p.add_argument("--lcrec-vocab", type=int, default=None,
+                   help="backbone vocabulary before the codebook tokens "
+                        "(Qwen2.5: 151936)")
+    p.add_argument("--lcrec-response-tokens", type=int, default=None,
+                   help="supervise only the last K positions per sample")
+    p.add_argument("--lcrec-eager", action="store_true",
+                   help="no hipGraph capture of the LCRec step")
     p.add_argument("--out", default=None)
     args = p.parse_args()
     device = torch.device("cuda:0") if torch.cuda.is_available() \
@@ -219,6 +256,10 @@ def main():
         if name == "lcrec":
             kw["full_size"] = args.lcrec_full
             kw["attn_impl"] = args.lcrec_attn
+            kw["loss_impl"] = args.lcrec_loss
+            kw["vocab"] = args.lcrec_vocab
+            kw["response_tokens"] = args.lcrec_response_tokens
+            kw["eager_step"] = args.lcrec_eager
         try:
             r = BENCHES[name](device, args.steps, args.warmup, **kw)
         except Exception as e:  # keep other models running

@@ -60,6 +60,11 @@ std::vector<torch::Tensor> softmax_ce_fwd(torch::Tensor logits,
 torch::Tensor softmax_ce_bwd(torch::Tensor dloss, torch::Tensor logits,
                              torch::Tensor targets, torch::Tensor lse,
                              torch::Tensor n_valid, int64_t ignore_index);
+std::vector<torch::Tensor> lce_inplace(torch::Tensor logits,
+                                       torch::Tensor targets,
+                                       torch::Tensor inv_n,
+                                       int64_t ignore_index, int64_t slices);
+int64_t lce_pick_slices(int64_t R, int64_t V);
 
 std::vector<torch::Tensor> sqdist_argmin(torch::Tensor x,
                                          torch::Tensor codebook);
@@ -147,6 +152,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hstu_attn_bwd", &genrec::hstu_attn_bwd, "HSTU fused attention bwd");
   m.def("softmax_ce_fwd", &genrec::softmax_ce_fwd, "fused CE forward");
   m.def("softmax_ce_bwd", &genrec::softmax_ce_bwd, "fused CE backward");
+  m.def("lce_inplace", &genrec::lce_inplace,
+        "in-place CE fwd+bwd over a logits chunk (lce_stats + lce_grad)",
+        py::arg("logits"), py::arg("targets"), py::arg("inv_n"),
+        py::arg("ignore_index"), py::arg("slices") = 0);
+  m.def("lce_pick_slices", &genrec::lce_pick_slices,
+        "column slices per row chosen for an [R, V] chunk");
   m.def("sqdist_argmin", &genrec::sqdist_argmin, "L2 dist + argmin");
   m.def("embedding_fwd", &genrec::embedding_fwd, "embedding gather");
   m.def("embedding_bwd", &genrec::embedding_bwd, "embedding scatter-add bwd");

@@ -60,14 +60,26 @@ def _attn_kwargs(attn_implementation: Optional[str]) -> Dict[str, str]:
     return {"attn_implementation": attn_implementation}
 
 
+LOSS_IMPLEMENTATIONS = (None, "genrec_lce")
+
+
 @ginlite.configurable(name="LCRec")
 class LCRec(nn.Module):
     def __init__(self, pretrained_path: Optional[str] = None,
                  config=None,
-                 attn_implementation: Optional[str] = None) -> None:
+                 attn_implementation: Optional[str] = None,
+                 loss_implementation: Optional[str] = None) -> None:
         super().__init__()
         from transformers import AutoModelForCausalLM, AutoTokenizer
 
+        if loss_implementation not in LOSS_IMPLEMENTATIONS:
+            raise ValueError(
+                f"loss_implementation {loss_implementation!r}: expected one "
+                f"of {LOSS_IMPLEMENTATIONS}")
+        # None = the backbone's own loss over full [B, L, V] logits;
+        # "genrec_lce" = ops.linear_cross_entropy on the hidden states
+        self.loss_implementation = loss_implementation
+        self._lce_fallback_logged = False
         self.attn_implementation = attn_implementation
         attn_kw = _attn_kwargs(attn_implementation)
         if pretrained_path and os.path.isdir(pretrained_path):
@@ -120,9 +132,51 @@ class LCRec(nn.Module):
         return {"input_ids": t, "prompt_seq_length": len(prompt_ids),
                 "attention_mask": torch.ones_like(t)}
 
+    def _lce_parts(self):
+        """(backbone, lm_head) when the wrapped model exposes them in the
+        plain causal-LM layout, else None (a PEFT wrapper, a biased head)."""
+        from transformers import PreTrainedModel
+
+        backbone = getattr(self.model, "model", None)
+        head = getattr(self.model, "lm_head", None)
+        # a PEFT wrapper forwards .model to the wrapped causal LM itself,
+        # so only a bare transformers model is taken apart
+        if isinstance(self.model, PreTrainedModel) \
+                and isinstance(backbone, nn.Module) \
+                and not hasattr(backbone, "lm_head") \
+                and isinstance(head, nn.Linear) and head.bias is None:
+            return backbone, head
+        if not self._lce_fallback_logged:
+            self._lce_fallback_logged = True
+            logger.warning(
+                "loss_implementation='genrec_lce' needs .model and a "
+                "bias-free .lm_head on %s; using the backbone's own loss",
+                type(self.model).__name__)
+        return None
+
     def forward(self, input_ids, attention_mask=None, labels=None, **kw):
+        if labels is not None and self.loss_implementation == "genrec_lce":
+            parts = self._lce_parts()
+            if parts is not None:
+                return self._forward_lce(parts, input_ids, attention_mask,
+                                         labels)
         return self.model(input_ids=input_ids, attention_mask=attention_mask,
                           labels=labels)
+
+    def _forward_lce(self, parts, input_ids, attention_mask, labels):
+        from transformers.modeling_outputs import CausalLMOutputWithPast
+
+        from genrec_amd import ops
+
+        backbone, head = parts
+        hidden = backbone(input_ids=input_ids,
+                          attention_mask=attention_mask).last_hidden_state
+        # the causal-LM shift: position i is scored against token i+1
+        shifted = F.pad(labels, (0, 1), value=-100)[..., 1:]
+        loss = ops.linear_cross_entropy(
+            hidden.reshape(-1, hidden.size(-1)), head.weight,
+            shifted.reshape(-1), ignore_index=-100)
+        return CausalLMOutputWithPast(loss=loss, logits=None)
 
     def save_pretrained(self, save_dir: str, **kwargs):
         self.model.save_pretrained(save_dir, **kwargs)

@@ -87,7 +87,9 @@ from genrec_amd.ops.attention import (  # noqa: E402
     gqa_flash_attention,
 )
 from genrec_amd.ops.quantize import residual_quantize_step  # noqa: E402
-from genrec_amd.ops.losses import softmax_ce, tied_softmax_ce, summed_ce  # noqa: E402
+from genrec_amd.ops.losses import (  # noqa: E402
+    softmax_ce, tied_softmax_ce, summed_ce, linear_cross_entropy,
+)
 from genrec_amd.ops.metrics import topk_hit_ranks  # noqa: E402
 from genrec_amd.ops.embedding import embedding  # noqa: E402
 from genrec_amd.ops.fused import (  # noqa: E402
@@ -113,6 +115,7 @@ __all__ = [
     "softmax_ce",
     "tied_softmax_ce",
     "summed_ce",
+    "linear_cross_entropy",
     "topk_hit_ranks",
     "embedding",
     "dropout_add",

@@ -177,3 +177,154 @@ def topk_hit_ranks(actual: Tensor, top_k: Tensor) -> Tensor:
     found = matches.any(dim=1)
     first = matches.float().argmax(dim=1)
     return torch.where(found, first, torch.full_like(first, K))
+
+
+# ------------------------------------------------- linear + cross-entropy
+#
+# loss = CE(hidden @ weight^T, targets) without ever holding [N, V]: the
+# supervised rows are gathered, the logits are formed a chunk of rows at a
+# time, each chunk is turned into its own gradient in place, and the two
+# gradient GEMMs run before the next chunk reuses the buffer. The loop below
+# is shared by the HIP op (ops/losses.py passes the kernel pair as
+# `chunk_fn`) and by the plain-PyTorch path, which is its CPU reference.
+
+LCE_CHUNK_ELEMS = 1 << 29   # logits elements per chunk (docs/kernels.md)
+
+
+def lce_default_chunk_rows(n_rows: int, vocab: int) -> int:
+    return max(1, min(max(n_rows, 1), LCE_CHUNK_ELEMS // max(vocab, 1)))
+
+
+def _lce_acc_dtype(dtype: torch.dtype) -> torch.dtype:
+    return torch.float64 if dtype == torch.float64 else torch.float32
+
+
+def lce_chunk_inplace(logits: Tensor, targets: Tensor, inv_n: Tensor,
+                      ignore_index: int, slices: int = 0):
+    """Plain-PyTorch twin of the lce_stats / lce_grad kernels: overwrite
+    logits[R, V] with inv_n * (softmax - onehot) (zeros for ignored rows)
+    and return (row_loss[R], lse[R])."""
+    V = logits.size(1)
+    x = logits.to(_lce_acc_dtype(logits.dtype))
+    lse = torch.logsumexp(x, dim=1)
+    ok = (targets != ignore_index) & (targets >= 0) & (targets < V)
+    t = torch.where(ok, targets, torch.zeros_like(targets)).unsqueeze(1)
+    row_loss = torch.where(ok, lse - x.gather(1, t).squeeze(1),
+                           torch.zeros_like(lse))
+    d = torch.exp(x - lse.unsqueeze(1))
+    d.scatter_add_(1, t, -ok.to(d.dtype).unsqueeze(1))
+    d.mul_(inv_n.to(d.dtype) * ok.unsqueeze(1))
+    logits.copy_(d)
+    return row_loss, lse
+
+
+def _lce_accumulate(dw: Tensor, a: Tensor, b: Tensor) -> None:
+    """dw += a @ b, with dw in the accumulation dtype."""
+    if a.dtype == dw.dtype:
+        dw.addmm_(a, b)
+    elif a.is_cuda:
+        # bf16 operands, fp32 accumulator updated in the GEMM epilogue
+        torch.addmm(dw, a, b, out_dtype=dw.dtype, out=dw)
+    else:
+        dw.addmm_(a.to(dw.dtype), b.to(dw.dtype))
+
+
+def lce_forward(hidden: Tensor, weight: Tensor, targets: Tensor,
+                ignore_index: int, reduction: str,
+                chunk_rows: Optional[int], compact: bool,
+                need_dhidden: bool, need_dweight: bool,
+                chunk_fn=lce_chunk_inplace, slices: int = 0):
+    """Compaction + chunk loop. Returns (loss, dhidden | None,
+    dweight | None); the gradients are those of `loss` itself."""
+    if reduction not in ("mean", "sum"):
+        raise ValueError(f"linear_cross_entropy: reduction {reduction!r}")
+    N, H = hidden.shape
+    V = weight.size(0)
+    dev, dtype = hidden.device, hidden.dtype
+    acc = _lce_acc_dtype(dtype)
+    valid = targets != ignore_index
+    idx = None
+    h, t = hidden, targets
+    if compact:
+        idx = valid.nonzero(as_tuple=True)[0]          # the one host sync
+        n_valid = idx.numel()
+        if n_valid == N:
+            idx = None
+        else:
+            h, t = hidden.index_select(0, idx), targets.index_select(0, idx)
+        inv_n = torch.full((1,), 1.0 / max(n_valid, 1), dtype=acc, device=dev)
+    else:
+        inv_n = valid.sum().clamp_min(1).to(acc).reciprocal().reshape(1)
+    if reduction == "sum":
+        inv_n = torch.ones(1, dtype=acc, device=dev)
+
+    n_rows = h.size(0)
+    cr = chunk_rows or lce_default_chunk_rows(n_rows, V)
+    cr = max(1, min(cr, max(n_rows, 1)))
+    n_chunks = (n_rows + cr - 1) // cr
+    # row stride padded to 8 elements: every row starts 16-byte aligned
+    buf = torch.empty(cr, (V + 7) // 8 * 8, dtype=dtype, device=dev)
+    w_t = weight.t()
+    dh = torch.empty_like(h) if need_dhidden else None
+    dw = None
+    if need_dweight and n_chunks != 1:
+        dw = torch.zeros(V, H, dtype=acc, device=dev)
+    row_losses = []
+    for i in range(0, n_rows, cr):
+        j = min(i + cr, n_rows)
+        lg = buf[:j - i, :V]
+        torch.mm(h[i:j], w_t, out=lg)
+        row_loss, _ = chunk_fn(lg, t[i:j], inv_n, ignore_index, slices)
+        row_losses.append(row_loss)
+        if need_dhidden:
+            torch.mm(lg, weight, out=dh[i:j])
+        if need_dweight:
+            if n_chunks == 1:
+                dw = lg.t() @ h[i:j]
+            else:
+                _lce_accumulate(dw, lg.t(), h[i:j])
+    if row_losses:
+        # one fixed-order reduce over all rows: bitwise reproducible
+        loss = torch.cat(row_losses).sum() * inv_n[0].to(row_losses[0].dtype)
+    else:
+        loss = torch.zeros((), dtype=acc, device=dev)
+    if need_dweight:
+        dw = dw.to(weight.dtype)
+    if need_dhidden and idx is not None:
+        dh = torch.zeros_like(hidden).index_copy_(0, idx, dh)
+    return loss, dh, dw
+
+
+def lce_backward(ctx, dloss: Tensor):
+    dh, dw = ctx.saved_tensors
+    return (None if dh is None else dh * dloss.to(dh.dtype),
+            None if dw is None else dw * dloss.to(dw.dtype))
+
+
+class _LinearCEEagerFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, hidden, weight, targets, ignore_index, reduction,
+                chunk_rows, compact, grad_enabled):
+        with torch.autocast(device_type=hidden.device.type, enabled=False):
+            loss, dh, dw = lce_forward(
+                hidden, weight, targets, ignore_index, reduction, chunk_rows,
+                compact, grad_enabled and ctx.needs_input_grad[0],
+                grad_enabled and ctx.needs_input_grad[1])
+        ctx.save_for_backward(dh, dw)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        return lce_backward(ctx, dloss) + (None,) * 6
+
+
+def linear_cross_entropy(hidden: Tensor, weight: Tensor, targets: Tensor,
+                         ignore_index: int = -100, reduction: str = "mean",
+                         chunk_rows: Optional[int] = None,
+                         compact: bool = True) -> Tensor:
+    """CE(hidden @ weight^T, targets) in plain PyTorch, same compaction
+    and chunk loop as the HIP op. With every row ignored the loss is 0."""
+    return _LinearCEEagerFn.apply(
+        hidden.reshape(-1, hidden.size(-1)).contiguous(), weight.contiguous(),
+        targets.reshape(-1).contiguous(), ignore_index, reduction,
+        chunk_rows, compact, torch.is_grad_enabled())

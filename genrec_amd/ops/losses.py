@@ -63,6 +63,85 @@ def tied_softmax_ce(hidden: Tensor, emb_weight: Tensor, targets: Tensor,
     return softmax_ce(logits, targets, ignore_index)
 
 
+class _LinearCEFn(torch.autograd.Function):
+    """Chunked linear + cross-entropy on the lce_stats / lce_grad kernels.
+
+    The number of supervised rows is known before the first chunk, so the
+    gradients of the loss are formed during forward (eager.lce_forward) and
+    backward only scales them by the incoming dloss.
+    """
+
+    @staticmethod
+    def forward(ctx, hidden, weight, targets, ignore_index, reduction,
+                chunk_rows, compact, grad_enabled, slices):
+        from genrec_amd import ops
+
+        ext = ops.ext()
+
+        def chunk_fn(logits, tgt, inv_n, ignore, s):
+            return ext.lce_inplace(logits, tgt, inv_n, ignore, s)
+
+        # nonzero() syncs with the host: not allowed while capturing
+        compact = compact and not torch.cuda.is_current_stream_capturing()
+        with torch.autocast(device_type="cuda", enabled=False):
+            loss, dh, dw = eager.lce_forward(
+                hidden, weight, targets, ignore_index, reduction, chunk_rows,
+                compact, grad_enabled and ctx.needs_input_grad[0],
+                grad_enabled and ctx.needs_input_grad[1],
+                chunk_fn=chunk_fn, slices=slices)
+        ctx.save_for_backward(dh, dw)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss: Tensor):
+        return eager.lce_backward(ctx, dloss) + (None,) * 7
+
+
+def linear_cross_entropy(hidden: Tensor, weight: Tensor, targets: Tensor,
+                         ignore_index: int = -100, reduction: str = "mean",
+                         chunk_rows: int | None = None, compact: bool = True,
+                         _slices: int = 0) -> Tensor:
+    """Cross-entropy of `hidden @ weight^T` against `targets` that never
+    forms the [N, V] logits (the LLM-head SFT loss).
+
+    hidden [..., H], weight [V, H], targets [...] int64; returns an fp32
+    scalar. Rows whose target is `ignore_index` carry no loss; with
+    `compact` they are dropped before the head GEMM (one host sync; skipped
+    automatically under stream capture). `chunk_rows` bounds the rows whose
+    logits exist at one time. With every row ignored the loss is 0.
+    `_slices` forces the kernels' column split (tests only).
+    """
+    import os
+
+    from genrec_amd import ops
+
+    dev_type = hidden.device.type
+    if torch.is_autocast_enabled(dev_type):
+        # what F.linear would do; grads come back in the parameter's dtype
+        ac = torch.get_autocast_dtype(dev_type)
+        hidden, weight = hidden.to(ac), weight.to(ac)
+    if not ops.use_hip(hidden):
+        return eager.linear_cross_entropy(hidden, weight, targets,
+                                          ignore_index, reduction,
+                                          chunk_rows, compact)
+    if os.environ.get("GENREC_DISABLE_LCE", "0") == "1":
+        flat_t = targets.reshape(-1)
+        loss = softmax_ce(
+            torch.nn.functional.linear(
+                hidden.reshape(-1, hidden.size(-1)), weight),
+            flat_t, ignore_index)
+        if reduction == "sum":
+            loss = loss * (flat_t != ignore_index).sum()
+        return loss.float()
+    if hidden.dtype != weight.dtype:
+        raise TypeError("linear_cross_entropy: hidden is "
+                        f"{hidden.dtype} but weight is {weight.dtype}")
+    return _LinearCEFn.apply(
+        hidden.reshape(-1, hidden.size(-1)).contiguous(), weight.contiguous(),
+        targets.reshape(-1).contiguous(), ignore_index, reduction,
+        chunk_rows, compact, torch.is_grad_enabled(), _slices)
+
+
 def summed_ce(logits: Tensor, targets: Tensor) -> Tensor:
     """TIGER loss: CE(reduction none) summed over sequence, mean over batch
     (tiger.py:232-240)."""

@@ -243,6 +243,9 @@ def train(
     max_text_len: Optional[int] = None,        # forwarded to the dataset
     # None = transformers default; "genrec_gqa" = project GQA flash kernel
     attn_implementation: Optional[str] = None,
+    # None = the backbone's own loss; "genrec_lce" = chunked linear + CE
+    # that never forms the [B*L, V] logits
+    loss_implementation: Optional[str] = None,
 ):
     if max_length is not None:
         max_seq_len = max_length
@@ -257,12 +260,14 @@ def train(
     device = ctx.device
 
     model = LCRec(pretrained_path=pretrained_path,
-                  attn_implementation=attn_implementation)
+                  attn_implementation=attn_implementation,
+                  loss_implementation=loss_implementation)
     if backbone_config is not None:
         from genrec_amd.models.lcrec import default_qwen_config
 
         model = LCRec(config=default_qwen_config(**backbone_config),
-                      attn_implementation=attn_implementation)
+                      attn_implementation=attn_implementation,
+                      loss_implementation=loss_implementation)
     model.add_codebook_tokens(n_codebooks, codebook_size)
     if checkpoint_path and os.path.isdir(checkpoint_path):
         model.load_pretrained(checkpoint_path)

@@ -22,6 +22,7 @@ sources = [
     "csrc/kernels/attention_mfma.hip",
     "csrc/kernels/hstu_attn.hip",
     "csrc/kernels/ce.hip",
+    "csrc/kernels/linear_ce.hip",
     "csrc/kernels/quantize.hip",
     "csrc/kernels/metrics.hip",
     "csrc/kernels/embedding.hip",

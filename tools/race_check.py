@@ -140,6 +140,19 @@ def build_cases():
     def ce():
         return ops.ext().softmax_ce_fwd(logits, targets, -100)[:2]
 
+    # linear + CE on the LLM head: 3 row chunks (fp32 dW accumulation),
+    # 3 column slices per row with a vector tail, some rows ignored
+    lh = torch.randn(130, 64, device=dev, dtype=torch.bfloat16)
+    lw = torch.randn(4099, 64, device=dev, dtype=torch.bfloat16) * 0.25
+    lt = torch.randint(0, 4099, (130,), device=dev)
+    lt[::3] = -100
+
+    def lce():
+        h, wt = lh.clone().requires_grad_(), lw.clone().requires_grad_()
+        loss = ops.linear_cross_entropy(h, wt, lt, chunk_rows=64, _slices=3)
+        loss.backward()
+        return loss.detach(), h.grad, wt.grad
+
     b = torch.randn(384, device=dev, dtype=torch.bfloat16)
 
     def ln_fwd():
@@ -169,6 +182,7 @@ def build_cases():
         ("layer_norm_bwd", ln_bwd, 0.0),
         ("colsum(vec4)", csum, 0.0),
         ("softmax_ce", ce, 0.0),
+        ("linear_cross_entropy(loss,dhidden,dweight)", lce, 0.0),
     ]
 
 
