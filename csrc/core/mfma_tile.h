@@ -7,7 +7,10 @@
 // A/B operands are natural 16-byte row chunks (lane l: row l&15, k-chunk
 // (l>>4)*8), so a fragment load is a single b128 read. Transposed images
 // are built from coalesced b128 natural-row global loads, an in-register
-// 8x8 butterfly transpose across the lane group and ONE b128 store.
+// 8x8 butterfly transpose across the lane group and ONE b128 store
+// (tile_store_tr), or not built at all: a dual-use image (swz_dual) is a
+// natural tile that frag_load_tr reads by columns with ds_read_b64_tr_b16
+// (attention_mfma; the other kernels still stage transposed copies).
 //
 // C/D fragment layout: lane l holds rows (l>>4)*4 + reg (reg = 0..3) of
 // column l&15 — a row reduction is an op over the column fragments
@@ -44,13 +47,62 @@ __device__ __forceinline__ int swz(int row, int byte_in_row,
   return row * row_bytes + (byte_in_row ^ ((row & 7) << 4));
 }
 
+// Dual-use image (128-byte rows only): one natural row-major tile that is
+// read by rows (frag_load, ds_read_b128) AND by columns (frag_load_tr,
+// ds_read_b64_tr_b16). The slot XOR is row bits {0,1,3} instead of {0,1,2}.
+// Bank = (byte/4) % 64 for both reads, so row bit 0 picks the 32-bank half
+// and the XOR has to separate the even (odd) rows that one lane group
+// touches in the same 16-byte slot column:
+//   b128 row read, groups {0-3,12-15,20-27} / {4-11,16-19,28-31}: rows>>1 in
+//     {0,1,6,7} share one slot, {2,3,4,5} the next -> (bit1,bit3) distinct;
+//   tr read, per 32-lane half two 4-row blocks 8 rows apart: rows>>1 in
+//     {0,1,4,5} or {2,3,6,7} on one 32-byte column pair -> (bit1,bit3)
+//     distinct, where (row&7) maps both blocks to the same banks (2-way).
+// Both reads are conflict-free; b128 / b64 stores bank as with swz().
+// Store and read a dual-use tile only through tile_off<true>.
+__device__ __forceinline__ int swz_dual(int row, int byte_in_row) {
+  return row * 128 + (byte_in_row ^ (((row & 3) | ((row & 8) >> 1)) << 4));
+}
+
+// the one offset function of a tile: DUAL picks the image
+template <bool DUAL>
+__device__ __forceinline__ int tile_off(int row, int byte_in_row,
+                                        int row_bytes) {
+  return DUAL ? swz_dual(row, byte_in_row) : swz(row, byte_in_row, row_bytes);
+}
+
 // load one 16x32 A/B fragment (8 bf16 = 16 B per lane) from a swizzled tile
+template <bool DUAL = false>
 __device__ __forceinline__ short8v frag_load(const char* base, int row0,
                                              int k0, int lane,
                                              int row_bytes = 128) {
   int row = row0 + (lane & 15);
   int byte = (k0 + ((lane >> 4) << 3)) * 2;
-  return *reinterpret_cast<const short8va*>(base + swz(row, byte, row_bytes));
+  return *reinterpret_cast<const short8va*>(
+      base + tile_off<DUAL>(row, byte, row_bytes));
+}
+
+// Transposed fragment load from a dual-use tile: the operand's k index runs
+// down the tile's rows [k_row0, k_row0+32) and its m/n index along columns
+// [col0, col0+16). Returns what frag_load(row0=col0, k0=k_row0) reads from
+// the transposed image, same k order, as two ds_read_b64_tr_b16: per
+// 16-lane group g the instruction gathers a 4-row x 16-column block and
+// hands lane i column i, so rows 8g..8g+3 fill elements 0..3 and rows
+// 8g+4..8g+7 elements 4..7. Lane 16g+4q+p supplies the address of row
+// k_row0+8g+q (+4), columns col0+4p..+3 (8-byte aligned; the 16-byte slot
+// XOR keeps them contiguous).
+// EXEC must be all ones: call only from wave-uniform control flow, on a
+// tile zero-padded to 64x64 so every lane's address is in bounds.
+__device__ __forceinline__ short8v frag_load_tr(const char* tile, int k_row0,
+                                                int col0, int lane) {
+  typedef __attribute__((address_space(3))) short4v lds_short4v;
+  const int row = k_row0 + ((lane >> 4) << 3) + ((lane >> 2) & 3);
+  const int byte = (col0 + ((lane & 3) << 2)) * 2;
+  short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (lds_short4v*)(tile + tile_off<true>(row, byte, 128)));
+  short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (lds_short4v*)(tile + tile_off<true>(row + 4, byte, 128)));
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
 // In-register 8x8 bf16 block transpose across the 8 lanes {8g+c : g=0..7}
@@ -86,17 +138,23 @@ __device__ __forceinline__ short8v load8(const __hip_bfloat16* base,
 }
 
 // natural store of 8 / 4 / 1 bf16 at (row, column d0) of a tile
+template <bool DUAL = false>
 __device__ __forceinline__ void tile_store(char* tile, int row, int d0,
                                            short8v val, int row_bytes = 128) {
-  *reinterpret_cast<short8va*>(tile + swz(row, d0 * 2, row_bytes)) = val;
+  *reinterpret_cast<short8va*>(
+      tile + tile_off<DUAL>(row, d0 * 2, row_bytes)) = val;
 }
+template <bool DUAL = false>
 __device__ __forceinline__ void tile_store(char* tile, int row, int d0,
                                            short4v val, int row_bytes = 128) {
-  *reinterpret_cast<short4va*>(tile + swz(row, d0 * 2, row_bytes)) = val;
+  *reinterpret_cast<short4va*>(
+      tile + tile_off<DUAL>(row, d0 * 2, row_bytes)) = val;
 }
+template <bool DUAL = false>
 __device__ __forceinline__ void tile_store(char* tile, int row, int d0,
                                            short val, int row_bytes = 128) {
-  *reinterpret_cast<short1a*>(tile + swz(row, d0 * 2, row_bytes)) = val;
+  *reinterpret_cast<short1a*>(
+      tile + tile_off<DUAL>(row, d0 * 2, row_bytes)) = val;
 }
 
 // transposed store: val is source (row, d0..d0+7); the 8 lanes (lane>>3)&7

@@ -1,24 +1,39 @@
 // MFMA fused attention (bf16) — gfx950 matrix-core path for K1/K4/K13.
 //
-// Forward: one 256-thread workgroup (4 waves) per (batch, head). Q, K and
-// V^T are staged in LDS as bf16 with the T2 XOR swizzle (byte ^= (row&7)<<4)
-// so ds_read_b128 fragment loads are conflict-free. Each wave owns a
-// 16-row q-strip: S = Q K^T runs as 4 column-fragments x (D/32) K-steps of
+// LDS images: every tile is staged ONCE, natural row-major, from coalesced
+// 16-byte global loads. A tile that some product needs by columns is a
+// dual-use image (mfma_tile.h): ds_read_b128 row reads (frag_load) and
+// ds_read_b64_tr_b16 transposed reads (frag_load_tr) of the same bytes are
+// both bank-conflict-free, so no transposed copy is built and no
+// cross-lane shuffle runs before the first MFMA.
+//
+// Forward: one 256-thread workgroup (4 waves) per (batch, head); tiles Q,
+// K (row reads), V and P^T (dual-use), 32 KiB. Each wave owns a 16-row
+// q-strip: S = Q K^T runs as 4 column-fragments x (D/32) K-steps of
 // v_mfma_f32_16x16x32_bf16; scale/bias/masks/softmax(or SiLU) are applied
 // on the accumulator fragments in-register (the C/D layout places row
 // (lane>>4)*4+reg, col lane&15 — a row reduction is an fmax/fadd over the
-// 4 column fragments followed by shuffle-xor over the 16-lane group);
-// P is written to LDS (bf16, swizzled) and consumed directly as the
-// A-operand of the P V MFMA. Scores never touch HBM; P is saved fp32 for
-// backward.
+// 4 column fragments followed by shuffle-xor over the 16-lane group).
+// A lane's four P values of one key column go to the P^T image [j][i] as
+// ONE 8-byte store; O = P V then reads both operands by columns (A from
+// P^T, B from V). Scores never touch HBM; P is saved fp32 for backward.
+// The bias / key-padding / additive-mask loads are issued with the tile
+// loads, ahead of the staging barrier.
 //
-// Backward: attn_bwd_ds_kernel computes dP = dO V^T with the same MFMA
-// geometry, applies the dropout/query-mask multiplier and the softmax
-// Jacobian (or SiLU') in-register, stages dS / dS^T / A_d^T in LDS, and
-// finishes dQ = dS K, dK = dS^T Q, dV = A_d^T dO as MFMA in the SAME
-// launch (no extra batched GEMMs, no extra global round-trips). All
-// global tensors are stride-parameterized so [B,L,H,D] transpose views
-// flow in/out without permute copies.
+// Backward: attn_bwd_ds_kernel stages dO, V, K, Q (dual-use, 6 tiles with
+// dS^T and A_d^T: 48.5 KiB, 3 workgroups per CU), computes dP = dO V^T by
+// row reads, applies the dropout/query-mask multiplier and the softmax
+// Jacobian (or SiLU') in-register, stores dS^T and A_d^T packed, and
+// finishes dQ = dS K (A: dS^T by columns, B: K by columns), dK = dS^T Q
+// (A: dS^T by rows, B: Q by columns), dV = A_d^T dO (A: A_d^T by rows,
+// B: dO by columns) as MFMA in the SAME launch (no extra batched GEMMs,
+// no extra global round-trips). P, the dropout mask and the query mask
+// are loaded with the tiles, ahead of the staging barrier. All global
+// tensors are stride-parameterized so [B,L,H,D] transpose views flow
+// in/out without permute copies.
+//
+// Every MFMA sees the operands, in the k order, that the earlier
+// shuffle-transposed images gave it: results are bitwise unchanged.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -29,8 +44,10 @@ namespace genrec {
 
 torch::Tensor colsum(torch::Tensor x);  // fused_elementwise.hip
 
+// 32 KiB of LDS lets 5 workgroups (5 waves/SIMD) share a CU; the second
+// launch bound keeps the register budget (<= 96) from lowering that.
 template <bool IS_SILU>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(256, 5)
 attn_fwd_mfma_kernel(
     const __hip_bfloat16* __restrict__ q,   // [B,H,Lq,D]
     const __hip_bfloat16* __restrict__ k,   // [B,H,Lk,D]
@@ -60,38 +77,82 @@ attn_fwd_mfma_kernel(
   const int q0 = blockIdx.y * q_tile;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* qs = smem;                 // [64][128B] swizzled bf16
-  char* ks = qs + TILE * 128;      // [64][128B]
-  char* vt = ks + TILE * 128;      // [64(d)][128B(j)] transposed V
-  char* ps = vt + TILE * 128;      // [64][128B] P (bf16)
+  char* qs = smem;                 // [64(i)][128B(d)] Q, row reads
+  char* ks = qs + TILE * 128;      // [64(j)][128B(d)] K, row reads
+  char* vs = ks + TILE * 128;      // [64(j)][128B(d)] V, dual-use image
+  char* pt = vs + TILE * 128;      // [64(j)][128B(i)] P^T, dual-use image
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  const int wid = tid >> 6;
+  // wave-uniform by construction; readfirstlane lets the compiler see it,
+  // so the branches around the transposed reads are scalar (EXEC all ones)
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int strip = wid * 16;            // this wave's q rows [strip, strip+16)
+  const int col_base = frag_col(lane);
+  const int row_grp = frag_row0(lane);   // rows row_grp..row_grp+3 (in strip)
 
-  // ---- stage: coalesced global rows -> swizzled LDS rows (zero-padded)
-  // each thread copies 8 bf16 (16 B); row-major walk
-  for (int idx = tid; idx < TILE * (TILE / 8); idx += blockDim.x) {
+  // ---- stage: coalesced global rows -> swizzled LDS rows (zero-padded).
+  // The 256 threads copy two 8-element (16 B) chunks of each tile;
+  // row-major walk. V stays natural: the PV B operand reads it by columns
+  // (frag_load_tr).
+  constexpr int NCH = TILE * (TILE / 8) / 256;
+  short8v qq8[NCH], kk8[NCH], vv8[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    int idx = tid + c * 256;
     int row = idx / (TILE / 8);
-    int c8 = idx % (TILE / 8);        // 8-elem chunk
-    int d0 = c8 * 8;
+    int d0 = (idx % (TILE / 8)) * 8;
     int qi = q0 + row;
-    tile_store(qs, row, d0,
-               load8(q, (int64_t)b * q_sb + h * q_sh + qi * q_sl + d0,
-                     qi < Lq && d0 < D));
-    tile_store(ks, row, d0,
-               load8(k, (int64_t)b * k_sb + h * k_sh + row * k_sl + d0,
-                     row < Lk && d0 < D));
-    // V^T tile: vt[d][j] = V[j][d]. Read V row-natural (ONE b128
-    // coalesced load), transpose the 8x8 block in-register across the
-    // lane group, store ONE b128 transposed row-chunk.
-    tile_store_tr(vt, row, d0, lane,
-                  load8(v, (int64_t)b * v_sb + h * v_sh + row * v_sl + d0,
-                        row < Lk && d0 < D));
+    qq8[c] = load8(q, (int64_t)b * q_sb + h * q_sh + qi * q_sl + d0,
+                   qi < Lq && d0 < D);
+    kk8[c] = load8(k, (int64_t)b * k_sb + h * k_sh + row * k_sl + d0,
+                   row < Lk && d0 < D);
+    vv8[c] = load8(v, (int64_t)b * v_sb + h * v_sh + row * v_sl + d0,
+                   row < Lk && d0 < D);
+  }
+
+  // ---- epilogue inputs (bias / key padding / additive mask) depend only
+  // on indices: issue them behind the tile loads and ahead of the staging
+  // barrier so one global-latency wait covers both
+  float bias_v[4][4], am_v[4][4];
+  bool kp_v[4];
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    int j = f * 16 + col_base;          // key col
+    kp_v[f] = (key_pad && j < Lk) ? key_pad[(int64_t)b * Lk + j] : false;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      int i = q0 + strip + row_grp + r;   // global q row
+      bool ok = (i < Lq) && (j < Lk);
+      float bv = 0.f, av = 0.f;
+      if (ok) {
+        if (bias_dim) {
+          int64_t bi = (bias_dim == 3) ? ((int64_t)h * Lq + i) * Lk + j
+                                       : idx4(b, h, i, j, H, Lq, Lk);
+          bv = bias_bf16 ? to_f32(bias_b[bi]) : bias_f[bi];
+        } else if (bias_bucket) {
+          // in-kernel rel-bias table gather (HSTU-style): no
+          // materialized [H,Lq,Lk] bias tensor traffic
+          bv = bias_f[h * n_buckets + bias_bucket[(int64_t)i * Lk + j]];
+        }
+        if (add_mask) av = add_mask[(int64_t)i * Lk + j];
+      }
+      bias_v[f][r] = bv;
+      am_v[f][r] = av;
+    }
+  }
+
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    int idx = tid + c * 256;
+    int row = idx / (TILE / 8);
+    int d0 = (idx % (TILE / 8)) * 8;
+    tile_store(qs, row, d0, qq8[c]);
+    tile_store(ks, row, d0, kk8[c]);
+    tile_store<true>(vs, row, d0, vv8[c]);
   }
   __syncthreads();
 
-  const int strip = wid * 16;            // this wave's q rows [strip, strip+16)
   const float inv_keep = dropout_p > 0.f ? 1.0f / (1.0f - dropout_p) : 1.0f;
 
   // ---- S = Q K^T : 4 column fragments
@@ -107,8 +168,6 @@ attn_fwd_mfma_kernel(
   }
 
   // ---- epilogue on fragments: scale + bias + masks
-  const int col_base = frag_col(lane);
-  const int row_grp = frag_row0(lane);   // rows row_grp..row_grp+3 (in strip)
   float s_val[4][4];                     // [fragment][reg]
 #pragma unroll
   for (int f = 0; f < 4; ++f) {
@@ -120,18 +179,10 @@ attn_fwd_mfma_kernel(
       bool ok = (i < Lq) && (j < Lk);
       if (ok) {
         s *= scale;
-        if (bias_dim) {
-          int64_t bi = (bias_dim == 3) ? ((int64_t)h * Lq + i) * Lk + j
-                                       : idx4(b, h, i, j, H, Lq, Lk);
-          s += bias_bf16 ? to_f32(bias_b[bi]) : bias_f[bi];
-        } else if (bias_bucket) {
-          // in-kernel rel-bias table gather (HSTU-style): no
-          // materialized [H,Lq,Lk] bias tensor traffic
-          s += bias_f[h * n_buckets + bias_bucket[(int64_t)i * Lk + j]];
-        }
+        if (bias_dim || bias_bucket) s += bias_v[f][r];
         if (causal && j > i) s = NEG_BIG;
-        if (key_pad && key_pad[(int64_t)b * Lk + j]) s = NEG_BIG;
-        if (add_mask) s += add_mask[(int64_t)i * Lk + j];
+        if (kp_v[f]) s = NEG_BIG;
+        if (add_mask) s += am_v[f][r];
       } else {
         s = -INFINITY;
       }
@@ -169,9 +220,12 @@ attn_fwd_mfma_kernel(
     }
   }
 
-  // ---- save P/S, apply post-softmax query mask + dropout, stash P in LDS
+  // ---- save P/S, apply post-softmax query mask + dropout, stash P^T in
+  // LDS: a lane's 4 r-values are consecutive i of one key column j, so they
+  // pack into ONE aligned 8-byte store at pt[j][i0..i0+3]
 #pragma unroll
   for (int f = 0; f < 4; ++f) {
+    short4v ppack;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       int i = q0 + strip + row_grp + r;
@@ -190,14 +244,15 @@ attn_fwd_mfma_kernel(
       } else {
         p = 0.f;
       }
-      // bf16 scatter into swizzled P tile (2 B per element)
-      tile_store(ps, strip + row_grp + r, j, bf16_bits(p));
+      ppack[r] = bf16_bits(p);
     }
+    tile_store<true>(pt, f * 16 + col_base, strip + row_grp, ppack);
   }
-  // wave-local: this wave only reads its own strip rows back
+  // wave-local: this wave only reads its own strip's 16 i-columns back
   __builtin_amdgcn_wave_barrier();
 
-  // ---- O = P V : A = P strip rows (k=j), B = vt rows (n=d)
+  // ---- O = P V : A = P^T columns (m=i, k=j), B = V columns (k=j, n=d),
+  // both by transposed reads (wave-uniform control flow only: EXEC all ones)
   float4v acc2[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f},
                      {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
   const int nfrag_d = (D + 15) / 16;
@@ -205,8 +260,8 @@ attn_fwd_mfma_kernel(
   for (int f = 0; f < 4; ++f) {
     if (f >= nfrag_d) break;
     for (int kk = 0; kk < TILE; kk += 32) {
-      short8v a = frag_load(ps, strip, kk, lane);
-      short8v bfr = frag_load(vt, f * 16, kk, lane);
+      short8v a = frag_load_tr(pt, kk, strip, lane);
+      short8v bfr = frag_load_tr(vs, kk, f * 16, lane);
       acc2[f] = mfma_bf16(a, bfr, acc2[f]);
     }
   }
@@ -234,12 +289,12 @@ attn_fwd_mfma_kernel(
 // cross-wave: each half reduces its 2-fragment partial over the 16-lane
 // group and writes it to a per-half LDS slot (dotbuf[2][64], 512 B — no
 // atomics: every slot has exactly one writer); one barrier later both
-// halves read the summed dot. dS/dS^T/A_d^T stores stay disjoint per half
+// halves read the summed dot. dS^T/A_d^T stores stay disjoint per half
 // (different column fragments -> different j rows of the transposed
 // tiles), and dQ/dK/dV split their OUTPUT d-fragments across the halves
-// with full k-loops. LDS grows by only 512 B, so still 2 blocks/CU but
-// 16 resident waves — double the latency hiding for the staging-bound
-// phases (round-1 PMC: 8 waves, ~49k LDS conflict cycles/dispatch).
+// with full k-loops. Six tiles + 512 B of LDS: 3 blocks/CU, 24 resident
+// waves (64-70 VGPRs allow more). The launch is exactly 512 threads: each
+// stages one 16-byte chunk of each of the four input tiles.
 template <bool IS_SILU>
 __global__ void __launch_bounds__(512)
 attn_bwd_ds_kernel(
@@ -272,50 +327,69 @@ attn_bwd_ds_kernel(
   const int b = bh / H, h = bh % H;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* dos = smem;                 // [64][128B] dO rows (A for dP)
-  char* vs = dos + TILE * 128;      // [64][128B] V rows (B for dP)
-  char* kt = vs + TILE * 128;       // [64(d)][128B(j)] K^T (B for dQ)
-  char* qt = kt + TILE * 128;       // [64(d)][128B(i)] Q^T (B for dK)
-  char* dot = qt + TILE * 128;      // [64(d)][128B(i)] dO^T (B for dV)
-  char* dsn = dot + TILE * 128;     // [64(i)][128B(j)] dS (A for dQ)
-  char* dst = dsn + TILE * 128;     // [64(j)][128B(i)] dS^T (A for dK)
+  // Every tile is a natural row-major dual-use image, staged once: dP
+  // reads dO and V by rows, dQ/dK/dV read K, Q and dO by columns.
+  char* dos = smem;                 // [64(i)][128B(d)] dO (A for dP, B for dV)
+  char* vs = dos + TILE * 128;      // [64(j)][128B(d)] V (B for dP)
+  char* ks = vs + TILE * 128;       // [64(j)][128B(d)] K (B for dQ)
+  char* qs = ks + TILE * 128;       // [64(i)][128B(d)] Q (B for dK)
+  char* dst = qs + TILE * 128;      // [64(j)][128B(i)] dS^T (A for dQ, dK)
   char* adt = dst + TILE * 128;     // [64(j)][128B(i)] A_d^T (A for dV)
   float* dotbuf = reinterpret_cast<float*>(adt + TILE * 128);  // [2][64]
   float* tab_lds = dotbuf + 2 * TILE;  // [n_buckets] table-grad partials
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  const int wid = tid >> 6;          // 0..7
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // 0..7, scalar
   const int pair = wid >> 1;         // strip owner
   const int half = wid & 1;          // fragment split
   const int fbase = half * 2;
+  const int strip = pair * 16;
+  const int col_base = frag_col(lane);
+  const int row_grp = frag_row0(lane);
 
   if (dtab_partial && tid < n_buckets) tab_lds[tid] = 0.f;
 
-  for (int idx = tid; idx < TILE * (TILE / 8); idx += blockDim.x) {
-    int row = idx / (TILE / 8);
-    int d0 = (idx % (TILE / 8)) * 8;
+  // stage: the 512 threads hold one 8-element chunk of each tile
+  short8v dd8, vv8, kk8, qq8;
+  const int st_row = tid / (TILE / 8);
+  const int st_d0 = (tid % (TILE / 8)) * 8;
+  {
+    const int row = st_row, d0 = st_d0;
     const bool q_ok = row < Lq && d0 < D, k_ok = row < Lk && d0 < D;
-    short8v dd8 = load8(
-        dout, (int64_t)b * do_sb + h * do_sh + row * do_sl + d0, q_ok);
-    short8v vv8 = load8(
-        v, (int64_t)b * v_sb + h * v_sh + row * v_sl + d0, k_ok);
-    short8v kk8 = load8(
-        k, (int64_t)b * k_sb + h * k_sh + row * k_sl + d0, k_ok);
-    short8v qq8 = load8(
-        q, (int64_t)b * q_sb + h * q_sh + row * q_sl + d0, q_ok);
-    tile_store(dos, row, d0, dd8);
-    tile_store(vs, row, d0, vv8);
-    // transposed images (row = d, cols = sequence positions): read each
-    // source row-natural — ONE b128 coalesced load per tensor —
-    // transpose 8x8 in-register, store ONE b128 per tensor.
-    tile_store_tr(kt, row, d0, lane, kk8);
-    tile_store_tr(qt, row, d0, lane, qq8);
-    tile_store_tr(dot, row, d0, lane, dd8);
+    dd8 = load8(dout, (int64_t)b * do_sb + h * do_sh + row * do_sl + d0, q_ok);
+    vv8 = load8(v, (int64_t)b * v_sb + h * v_sh + row * v_sl + d0, k_ok);
+    kk8 = load8(k, (int64_t)b * k_sb + h * k_sh + row * k_sl + d0, k_ok);
+    qq8 = load8(q, (int64_t)b * q_sb + h * q_sh + row * q_sl + d0, q_ok);
   }
+
+  // P (or S), the dropout mask and the query mask depend only on indices:
+  // issue them behind the tile loads and ahead of the staging barrier so
+  // one global-latency wait covers both instead of a second one after the
+  // dP MFMAs
+  float pv[2][4], qm_v[4];
+  unsigned char dm_v[2][4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    int i = strip + row_grp + r;
+    qm_v[r] = (!IS_SILU && query_mask && i < Lq)
+                  ? query_mask[(int64_t)b * Lq + i] : 1.f;
+#pragma unroll
+    for (int fi = 0; fi < 2; ++fi) {
+      int j = (fbase + fi) * 16 + col_base;
+      bool ok = (i < Lq) && (j < Lk);
+      pv[fi][r] = ok ? p_saved[idx4(b, h, i, j, H, Lq, Lk)] : 0.f;
+      dm_v[fi][r] = (!IS_SILU && dropout_p > 0.f && ok)
+                        ? drop_mask[idx4(b, h, i, j, H, Lq, Lk)] : 0;
+    }
+  }
+
+  tile_store<true>(dos, st_row, st_d0, dd8);
+  tile_store<true>(vs, st_row, st_d0, vv8);
+  tile_store<true>(ks, st_row, st_d0, kk8);
+  tile_store<true>(qs, st_row, st_d0, qq8);
   __syncthreads();
 
-  const int strip = pair * 16;
   const float inv_keep = dropout_p > 0.f ? 1.0f / (1.0f - dropout_p) : 1.0f;
 
   // dP = dO V^T : A = dO strip rows (k=d), B = V rows (n=j, k=d).
@@ -324,15 +398,13 @@ attn_bwd_ds_kernel(
 #pragma unroll
   for (int fi = 0; fi < 2; ++fi) {
     for (int kk = 0; kk < D; kk += 32) {
-      short8v a = frag_load(dos, strip, kk, lane);
-      short8v bfr = frag_load(vs, (fbase + fi) * 16, kk, lane);
+      short8v a = frag_load<true>(dos, strip, kk, lane);
+      short8v bfr = frag_load<true>(vs, (fbase + fi) * 16, kk, lane);
       acc[fi] = mfma_bf16(a, bfr, acc[fi]);
     }
   }
 
-  const int col_base = frag_col(lane);
-  const int row_grp = frag_row0(lane);
-  float pv[2][4], da[2][4], ad[2][4];
+  float da[2][4], ad[2][4];
 #pragma unroll
   for (int fi = 0; fi < 2; ++fi) {
 #pragma unroll
@@ -340,15 +412,12 @@ attn_bwd_ds_kernel(
       int i = strip + row_grp + r;
       int j = (fbase + fi) * 16 + col_base;
       bool ok = (i < Lq) && (j < Lk);
-      float p = ok ? p_saved[idx4(b, h, i, j, H, Lq, Lk)] : 0.f;
+      float p = pv[fi][r];    // P (softmax) or S (silu)
       float m = 1.f;
       if (!IS_SILU && ok) {
-        if (query_mask) m *= query_mask[(int64_t)b * Lq + i];
-        if (dropout_p > 0.f) {
-          m *= drop_mask[idx4(b, h, i, j, H, Lq, Lk)] ? inv_keep : 0.f;
-        }
+        if (query_mask) m *= qm_v[r];
+        if (dropout_p > 0.f) m *= dm_v[fi][r] ? inv_keep : 0.f;
       }
-      pv[fi][r] = p;          // P (softmax) or S (silu)
       da[fi][r] = ok ? acc[fi][r] * (IS_SILU ? 1.f : m) : 0.f;
       ad[fi][r] = IS_SILU ? (ok ? p * sigmoidf_dev(p) : 0.f) : p * m;
     }
@@ -387,12 +456,12 @@ attn_bwd_ds_kernel(
     }
   }
 
-  // stash dS (natural + transposed) and A_d^T in LDS; optional global dS.
-  // For the transposed tiles a lane's 4 r-values land on consecutive
-  // columns of row j, so they pack into ONE aligned 8-byte ds_write
-  // (4x fewer LDS stores than per-element bf16 scatter -> fewer bank
-  // conflict cycles; rocprofv3 SQ_LDS_BANK_CONFLICT was dominated by
-  // these stores). Halves write disjoint j rows / column fragments.
+  // stash dS^T and A_d^T in LDS; optional global dS. A lane's 4 r-values
+  // land on consecutive columns of row j, so they pack into ONE aligned
+  // 8-byte ds_write (4x fewer LDS stores than per-element bf16 scatter ->
+  // fewer bank conflict cycles; rocprofv3 SQ_LDS_BANK_CONFLICT was
+  // dominated by these stores). dQ reads dS^T by columns, so there is no
+  // natural dS image. Halves write disjoint j rows / column fragments.
   const int i0 = strip + row_grp;  // multiple of 4 -> byte i0*2 is 8B-aligned
 #pragma unroll
   for (int fi = 0; fi < 2; ++fi) {
@@ -405,7 +474,6 @@ attn_bwd_ds_kernel(
       float aval = (i < Lq && j < Lk) ? ad[fi][r] : 0.f;
       dpack[r] = bf16_bits(dval * scale);
       apack[r] = bf16_bits(aval);
-      tile_store(dsn, i, j, dpack[r]);
       if (ds_saved && i < Lq && j < Lk) {
         ds_saved[idx4(b, h, i, j, H, Lq, Lk)] = __float2bfloat16(dval);
       }
@@ -415,12 +483,12 @@ attn_bwd_ds_kernel(
       }
     }
     int j = (fbase + fi) * 16 + col_base;
-    tile_store(dst, j, i0, dpack);
-    tile_store(adt, j, i0, apack);
+    tile_store<true>(dst, j, i0, dpack);
+    tile_store<true>(adt, j, i0, apack);
   }
-  // dQ's A-operand (dsn strip rows) now mixes both halves' column
-  // fragments, and dK/dV read all pairs' dS^T/A_d^T columns: one
-  // workgroup barrier covers every consumer below.
+  // dQ's A-operand (this strip's i columns of dS^T) mixes both halves'
+  // j rows, and dK/dV read all pairs' dS^T/A_d^T columns: one workgroup
+  // barrier covers every consumer below.
   __syncthreads();
   if (dtab_partial && tid < n_buckets) {
     // one partial row per (b,h) block; reduced deterministically on the
@@ -435,8 +503,8 @@ attn_bwd_ds_kernel(
     for (int fi = 0; fi < 2; ++fi) {
       if (fbase + fi >= nfrag_d) break;
       for (int kk = 0; kk < TILE; kk += 32) {
-        short8v a = frag_load(dsn, strip, kk, lane);
-        short8v bfr = frag_load(kt, (fbase + fi) * 16, kk, lane);
+        short8v a = frag_load_tr(dst, kk, strip, lane);
+        short8v bfr = frag_load_tr(ks, kk, (fbase + fi) * 16, lane);
         accq[fi] = mfma_bf16(a, bfr, accq[fi]);
       }
     }
@@ -462,11 +530,11 @@ attn_bwd_ds_kernel(
     for (int fi = 0; fi < 2; ++fi) {
       if (fbase + fi >= nfrag_d) break;
       for (int kk = 0; kk < TILE; kk += 32) {
-        short8v a1 = frag_load(dst, strip, kk, lane);
-        short8v b1 = frag_load(qt, (fbase + fi) * 16, kk, lane);
+        short8v a1 = frag_load<true>(dst, strip, kk, lane);
+        short8v b1 = frag_load_tr(qs, kk, (fbase + fi) * 16, lane);
         acck[fi] = mfma_bf16(a1, b1, acck[fi]);
-        short8v a2 = frag_load(adt, strip, kk, lane);
-        short8v b2 = frag_load(dot, (fbase + fi) * 16, kk, lane);
+        short8v a2 = frag_load<true>(adt, strip, kk, lane);
+        short8v b2 = frag_load_tr(dos, kk, (fbase + fi) * 16, lane);
         accv[fi] = mfma_bf16(a2, b2, accv[fi]);
       }
     }
@@ -639,7 +707,7 @@ std::vector<torch::Tensor> attn_bwd_mfma(
     qm_f = query_mask->to(torch::kFloat32).contiguous();
   dim3 block(512);  // 8 waves: pairs own strips, halves split fragments
   dim3 grid(B * H);
-  size_t smem = 8 * TILE * 128 + 2 * TILE * sizeof(float)
+  size_t smem = 6 * TILE * 128 + 2 * TILE * sizeof(float)
       + (table_mode ? (size_t)n_buckets * sizeof(float) : 0);
   auto stream = at::cuda::getCurrentHIPStream();
 
