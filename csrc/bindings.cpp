@@ -126,6 +126,15 @@ std::vector<torch::Tensor> gqa_attn_bwd(
     torch::Tensor out, torch::Tensor lse,
     c10::optional<torch::Tensor> key_pad, double scale, bool causal);
 
+torch::Tensor beam_attn_fwd(torch::Tensor q, torch::Tensor k_pre,
+                            torch::Tensor v_pre,
+                            c10::optional<torch::Tensor> pre_pad,
+                            torch::Tensor k_suf, torch::Tensor v_suf,
+                            torch::Tensor anc, int64_t t, double scale,
+                            int64_t splits);
+int64_t beam_attn_pick_splits(int64_t B, int64_t Hkv, int64_t rows,
+                              int64_t Lp);
+
 }  // namespace genrec
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -191,4 +200,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "grouped-query flash attention fwd (D 64/128) -> (out, lse)");
   m.def("gqa_attn_bwd", &genrec::gqa_attn_bwd,
         "grouped-query flash attention bwd (deterministic) -> (dq, dk, dv)");
+  m.def("beam_attn_fwd", &genrec::beam_attn_fwd,
+        "shared-prefix beam-search decode attention (D 64/128) -> out",
+        py::arg("q"), py::arg("k_pre"), py::arg("v_pre"), py::arg("pre_pad"),
+        py::arg("k_suf"), py::arg("v_suf"), py::arg("anc"), py::arg("t"),
+        py::arg("scale"), py::arg("splits") = 0);
+  m.def("beam_attn_pick_splits", &genrec::beam_attn_pick_splits,
+        "prefix splits chosen for (B, Hkv, W*g rows, Lp)");
 }

@@ -1,5 +1,6 @@
 // Tile primitives shared by the v_mfma_f32_16x16x32_bf16 kernels
-// (attention_mfma, attention_flash, hstu_attn, attention_gqa, skinny_gemm).
+// (attention_mfma, attention_flash, hstu_attn, attention_gqa, attention_beam,
+// skinny_gemm).
 //
 // LDS image: a tile is 64 rows of bf16 with 128-byte rows (64 columns) or
 // 256-byte rows (128 columns), stored with an XOR swizzle on 16-byte slots
@@ -172,6 +173,33 @@ __device__ __forceinline__ void tile_store_tr(char* tile, int row, int d0,
 #pragma unroll
   for (int e = 0; e < 8; ++e) pack[e] = t[e];
   tile_store(tile, d0 + g, row & ~7, pack);
+}
+
+// Stage 64 rows x D of a [*, L, D]-strided operand (row stride sl) into a
+// natural tile nat[64][D] and/or a transposed tile tr[D][64] (256 threads).
+// Rows at or beyond L, and rows that row_pad (null | [L]) marks, are zero.
+// Items are walked in 64-wide column halves so that the 8 lanes
+// (lane>>3)&7 of a wave hold 8 consecutive rows of one 8-column chunk,
+// which is what the in-register transpose needs. Every thread runs the same
+// number of iterations (shuffles inside).
+template <int D, bool NAT, bool TR>
+__device__ __forceinline__ void gstage(const __hip_bfloat16* __restrict__ src,
+                                       int64_t sl, int r0, int L, char* nat,
+                                       char* tr, int tid,
+                                       const bool* row_pad = nullptr) {
+  const int lane = tid & 63;
+  for (int idx = tid; idx < TILE * (D / 8); idx += 256) {
+    int half = idx >> 9;          // 512 items per 64-column half
+    int rem = idx & 511;
+    int row = rem >> 3;
+    int d0 = half * 64 + (rem & 7) * 8;
+    int gi = r0 + row;
+    bool live = gi < L;
+    if (live && row_pad) live = !row_pad[gi];
+    short8v val = load8(src, (int64_t)gi * sl + d0, live);
+    if (NAT) tile_store(nat, row, d0, val, D * 2);
+    if (TR) tile_store_tr(tr, row, d0, lane, val);
+  }
 }
 
 __device__ __forceinline__ float4v mfma_bf16(short8v a, short8v b,

@@ -36,29 +36,6 @@ namespace genrec {
 
 namespace {
 
-// Stage 64 rows x D of a [*, L, D]-strided operand (row stride sl) into a
-// natural tile nat[64][D] and/or a transposed tile tr[D][64]. Rows at or
-// beyond L are zero. Items are walked in 64-wide column halves so that the
-// 8 lanes (lane>>3)&7 of a wave hold 8 consecutive rows of one 8-column
-// chunk, which is what the in-register transpose needs. Every thread runs
-// the same number of iterations (shuffles inside).
-template <int D, bool NAT, bool TR>
-__device__ __forceinline__ void gstage(const __hip_bfloat16* __restrict__ src,
-                                       int64_t sl, int r0, int L, char* nat,
-                                       char* tr, int tid) {
-  const int lane = tid & 63;
-  for (int idx = tid; idx < TILE * (D / 8); idx += 256) {
-    int half = idx >> 9;          // 512 items per 64-column half
-    int rem = idx & 511;
-    int row = rem >> 3;
-    int d0 = half * 64 + (rem & 7) * 8;
-    int gi = r0 + row;
-    short8v val = load8(src, (int64_t)gi * sl + d0, gi < L);
-    if (NAT) tile_store(nat, row, d0, val, D * 2);
-    if (TR) tile_store_tr(tr, row, d0, lane, val);
-  }
-}
-
 // ------------------------------------------------------------------ forward
 
 template <int D>

@@ -61,6 +61,7 @@ def _attn_kwargs(attn_implementation: Optional[str]) -> Dict[str, str]:
 
 
 LOSS_IMPLEMENTATIONS = (None, "genrec_lce")
+BEAM_CACHES = (None, "shared_prefix")
 
 
 @ginlite.configurable(name="LCRec")
@@ -203,8 +204,16 @@ class LCRec(nn.Module):
         allowed_token_fn: Optional[Callable[[int], bool]] = None,
         eos_token_id: Optional[int] = None,
         temperature: float = 1.0,
+        beam_cache: Optional[str] = None,
     ) -> List[List[Tuple[torch.Tensor, float]]]:
         """Batched KV-cached constrained beam search.
+
+        beam_cache: None expands the prefill's KV cache W times and
+        reorders all of it after every step; "shared_prefix" keeps one copy
+        of the prompt's K/V per prompt plus per-beam suffix slots and a
+        lineage table (SharedPrefixBeamCache) and runs each decode step's
+        attention through ops.beam_decode_attention. It needs
+        attn_implementation="genrec_gqa" and max_new_tokens <= 16.
 
         allowed_token_ids: per-step 1-D tensors of legal token ids (the
         device-mask replacement for the reference's per-token Python
@@ -212,6 +221,22 @@ class LCRec(nn.Module):
         given (applied as a precomputed vocab mask).
         """
         from transformers import DynamicCache
+
+        if beam_cache not in BEAM_CACHES:
+            raise ValueError(f"beam_cache {beam_cache!r}: expected one of "
+                             f"{BEAM_CACHES}")
+        if beam_cache == "shared_prefix":
+            from genrec_amd.ops.attention import BEAM_MAX_SUFFIX
+
+            if self.attn_implementation != "genrec_gqa":
+                raise ValueError(
+                    'beam_cache="shared_prefix" requires '
+                    'attn_implementation="genrec_gqa", got '
+                    f"{self.attn_implementation!r}")
+            if max_new_tokens > BEAM_MAX_SUFFIX:
+                raise ValueError(
+                    'beam_cache="shared_prefix" supports max_new_tokens <= '
+                    f"{BEAM_MAX_SUFFIX}, got {max_new_tokens}")
 
         device = input_ids.device
         B, L = input_ids.shape
@@ -228,20 +253,63 @@ class LCRec(nn.Module):
             keep = [allowed_token_fn(t) for t in range(V)]
             fn_mask = torch.tensor(keep, dtype=torch.bool, device=device)
 
-        # prefill once per batch row
+        # prefill once per batch row; decode(last, step) -> [B*W, V] logits
+        # of one step, hop(parent) moves the cache to the surviving beams
         cache = DynamicCache()
-        out = self.model(input_ids=input_ids, attention_mask=attention_mask,
-                         past_key_values=cache, use_cache=True)
-        logits = out.logits[:, -1, :] / temperature          # [B, V]
-        if hasattr(cache, "batch_repeat_interleave"):
-            cache.batch_repeat_interleave(W)
-        else:  # older transformers: expand via legacy tuples
-            idx = torch.arange(B, device=device).repeat_interleave(W)
-            legacy = tuple(
-                (k.index_select(0, idx), v.index_select(0, idx))
-                for k, v in cache.to_legacy_cache())
-            cache = DynamicCache.from_legacy_cache(legacy)
-        attn = attention_mask.repeat_interleave(W, dim=0)     # [B*W, L]
+        if beam_cache == "shared_prefix":
+            from genrec_amd.modules.hf_attention import SharedPrefixBeamCache
+
+            out = self.model(input_ids=input_ids,
+                             attention_mask=attention_mask,
+                             past_key_values=cache, use_cache=True,
+                             logits_to_keep=1)
+            logits = out.logits[:, -1, :] / temperature      # [B, V]
+            beams = SharedPrefixBeamCache.from_prefill(
+                cache, W, max(max_new_tokens - 1, 1),
+                pre_pad=attention_mask == 0)
+
+            def decode(last: torch.Tensor, step: int) -> torch.Tensor:
+                # the position the expanded cache's length would give: pads
+                # counted, the same for every beam
+                pos = torch.full((1, 1), L + step - 1, dtype=torch.long,
+                                 device=device)
+                out = self.model(input_ids=last,
+                                 attention_mask={"full_attention": None},
+                                 position_ids=pos, past_key_values=beams,
+                                 use_cache=True, logits_to_keep=1,
+                                 genrec_beam_state=beams)
+                return out.logits[:, -1, :]
+
+            hop = beams.advance
+        else:
+            out = self.model(input_ids=input_ids,
+                             attention_mask=attention_mask,
+                             past_key_values=cache, use_cache=True)
+            logits = out.logits[:, -1, :] / temperature      # [B, V]
+            if hasattr(cache, "batch_repeat_interleave"):
+                cache.batch_repeat_interleave(W)
+            else:  # older transformers: expand via legacy tuples
+                idx = torch.arange(B, device=device).repeat_interleave(W)
+                legacy = tuple(
+                    (k.index_select(0, idx), v.index_select(0, idx))
+                    for k, v in cache.to_legacy_cache())
+                cache = DynamicCache.from_legacy_cache(legacy)
+            attn = attention_mask.repeat_interleave(W, dim=0)  # [B*W, L]
+
+            def decode(last: torch.Tensor, step: int) -> torch.Tensor:
+                nonlocal attn
+                attn = torch.cat([attn, torch.ones(
+                    B * W, 1, dtype=attn.dtype, device=device)], dim=1)
+                out = self.model(input_ids=last, attention_mask=attn,
+                                 past_key_values=cache, use_cache=True)
+                return out.logits[:, -1, :]
+
+            def hop(parent: torch.Tensor) -> None:
+                nonlocal attn
+                flat_parent = (torch.arange(B, device=device).unsqueeze(1)
+                               * W + parent).reshape(-1)
+                cache.reorder_cache(flat_parent)
+                attn = attn.index_select(0, flat_parent)
 
         def legal(step_logits: torch.Tensor, step: int) -> torch.Tensor:
             lp = F.log_softmax(step_logits, dim=-1)
@@ -264,11 +332,7 @@ class LCRec(nn.Module):
             if bool(finished.all()):
                 break
             last = beam_tokens[:, :, -1].reshape(B * W, 1)
-            attn = torch.cat([attn, torch.ones(B * W, 1, dtype=attn.dtype,
-                                               device=device)], dim=1)
-            out = self.model(input_ids=last, attention_mask=attn,
-                             past_key_values=cache, use_cache=True)
-            logits = out.logits[:, -1, :] / temperature       # [B*W, V]
+            logits = decode(last, step) / temperature         # [B*W, V]
             lp = legal(logits, step).view(B, W, V)
             # finished beams keep their score and emit only eos
             lp = torch.where(
@@ -288,10 +352,7 @@ class LCRec(nn.Module):
                 tok.unsqueeze(-1),
             ], dim=-1)
             finished = finished.gather(1, parent) | (tok == eos)
-            flat_parent = (torch.arange(B, device=device).unsqueeze(1) * W
-                           + parent).reshape(-1)
-            cache.reorder_cache(flat_parent)
-            attn = attn.index_select(0, flat_parent)
+            hop(parent)
 
         results: List[List[Tuple[torch.Tensor, float]]] = []
         for b in range(B):

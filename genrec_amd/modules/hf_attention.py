@@ -17,17 +17,90 @@ Select it with `attn_implementation="genrec_gqa"` on `LCRec` /
 `Query2Embedding`, or `model.set_attn_implementation("genrec_gqa")`.
 Configurations the kernel does not cover fall back to the stock `sdpa`
 function; nothing that works with `sdpa` raises here.
+
+Beam-search decode can hand the adapter a `SharedPrefixBeamCache` as the
+extra forward keyword `genrec_beam_state`: the step's attention then runs
+`ops.beam_decode_attention` on the cache's one-copy-per-prompt prefix and
+its per-beam suffix slots (LCRec.generate_topk, beam_cache="shared_prefix").
 """
 
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
-from genrec_amd.ops.attention import gqa_flash_attention, gqa_kernel_supported
+from genrec_amd.ops.attention import (
+    BEAM_MAX_SUFFIX, beam_decode_attention, gqa_flash_attention,
+    gqa_kernel_supported,
+)
 
 NAME = "genrec_gqa"
+
+
+class SharedPrefixBeamCache:
+    """KV cache of a beam search whose W beams per prompt share the prompt.
+
+    Holds, per layer, the prefill's keys/values [B,Hkv,Lp,D] exactly as the
+    prefill left them (no expansion to B*W) and suffix slots k_suf/v_suf
+    [B,T,W,Hkv,D]: slot s is what the beam sitting in position w wrote at
+    decode step s. One lineage table anc [B,W,T] (int32, shared by all
+    layers) says whose slot-s entry beam w inherits, so a beam hop rewrites
+    W*T integers instead of gathering every K/V tensor.
+
+    Duck-types the part of `transformers.Cache` a decoder layer uses:
+    `update(k, v, layer_idx)` and `get_seq_length()`. Per decode step: every
+    layer's `update` copies the step's projections into slot `t`, attention
+    reads slots 0..t through `anc`, then `advance(parent)` is called once.
+    """
+
+    def __init__(self, k_pre: List[torch.Tensor], v_pre: List[torch.Tensor],
+                 beam_width: int, max_suffix: int,
+                 pre_pad: Optional[torch.Tensor] = None) -> None:
+        if not 1 <= max_suffix <= BEAM_MAX_SUFFIX:
+            raise ValueError(f"max_suffix {max_suffix}: expected 1.."
+                             f"{BEAM_MAX_SUFFIX}")
+        B, Hkv, _, D = k_pre[0].shape
+        self.k_pre, self.v_pre = list(k_pre), list(v_pre)
+        self.pre_pad = pre_pad                    # [B, Lp] bool | None
+        self.beam_width, self.max_suffix = beam_width, max_suffix
+        shape = (B, max_suffix, beam_width, Hkv, D)
+        self.k_suf = [k.new_zeros(shape) for k in k_pre]
+        self.v_suf = [v.new_zeros(shape) for v in v_pre]
+        self.t = 0                                # committed suffix slots
+        self._own = torch.arange(beam_width, dtype=torch.int32,
+                                 device=k_pre[0].device)
+        self.anc = torch.zeros(B, beam_width, max_suffix, dtype=torch.int32,
+                               device=k_pre[0].device)
+        self.anc[:, :, 0] = self._own
+
+    @classmethod
+    def from_prefill(cls, cache, beam_width: int, max_suffix: int,
+                     pre_pad: Optional[torch.Tensor] = None):
+        """From the DynamicCache a prefill over the B prompts filled."""
+        return cls([layer.keys for layer in cache.layers],
+                   [layer.values for layer in cache.layers],
+                   beam_width, max_suffix, pre_pad)
+
+    def get_seq_length(self, layer_idx: int = 0) -> int:
+        return self.k_pre[layer_idx].size(2) + self.t
+
+    def update(self, key_states: torch.Tensor, value_states: torch.Tensor,
+               layer_idx: int, *args, **kwargs):
+        """Store one decode step's [B*W,Hkv,1,D] projections in slot t."""
+        dst = self.k_suf[layer_idx][:, self.t]    # [B,W,Hkv,D]
+        dst.copy_(key_states[:, :, 0].reshape(dst.shape))
+        self.v_suf[layer_idx][:, self.t].copy_(
+            value_states[:, :, 0].reshape(dst.shape))
+        return key_states, value_states
+
+    def advance(self, parent: torch.Tensor) -> None:
+        """Commit slot t after a beam hop: beam w continues parent[b,w]."""
+        idx = parent.unsqueeze(-1).expand(-1, -1, self.max_suffix)
+        self.anc = self.anc.gather(1, idx)
+        self.t += 1
+        if self.t < self.max_suffix:
+            self.anc[:, :, self.t] = self._own
 
 
 def _key_pad_from_mask(attention_mask: torch.Tensor, batch: int,
@@ -67,6 +140,18 @@ def genrec_gqa_attention_forward(
         return sdpa_attention_forward(module, query, key, value,
                                       attention_mask, dropout=dropout,
                                       scaling=scaling, **kwargs)
+
+    beam_state = kwargs.pop("genrec_beam_state", None)
+    if beam_state is not None:
+        if kwargs.get("sliding_window") is not None or query.size(2) != 1:
+            raise ValueError("genrec_beam_state serves single-token decode "
+                             "steps of full-attention layers only")
+        scale = scaling if scaling is not None else query.size(-1) ** -0.5
+        i, st = module.layer_idx, beam_state
+        out = beam_decode_attention(
+            query, st.k_pre[i], st.v_pre[i], st.k_suf[i], st.v_suf[i],
+            st.anc, st.t + 1, pre_pad=st.pre_pad, scale=scale)
+        return out, None                      # [B*W, 1, Hq, D]
 
     lq, lk = query.size(2), key.size(2)
     is_causal = kwargs.get("is_causal")

@@ -85,6 +85,8 @@ from genrec_amd.ops.attention import (  # noqa: E402
     hstu_pointwise_attention,
     hstu_fused_attention,
     gqa_flash_attention,
+    beam_decode_attention,
+    beam_decode_supported,
 )
 from genrec_amd.ops.quantize import residual_quantize_step  # noqa: E402
 from genrec_amd.ops.losses import (  # noqa: E402
@@ -111,6 +113,8 @@ __all__ = [
     "hstu_pointwise_attention",
     "hstu_fused_attention",
     "gqa_flash_attention",
+    "beam_decode_attention",
+    "beam_decode_supported",
     "residual_quantize_step",
     "softmax_ce",
     "tied_softmax_ce",

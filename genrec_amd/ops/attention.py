@@ -465,3 +465,81 @@ def gqa_flash_attention(
         return _GqaFlashAttnFn.apply(q, k, v, kp, float(scale), bool(causal))
     return eager.gqa_attention(q, k, v, key_pad_mask=key_pad_mask,
                                scale=scale, causal=causal)
+
+
+BEAM_MAX_SUFFIX = 16   # suffix slots the decode kernel unrolls over
+
+
+def beam_decode_supported(q: Tensor, k_pre: Tensor, v_pre: Tensor,
+                          k_suf: Tensor, v_suf: Tensor, anc: Tensor) -> bool:
+    """True iff beam_decode_attention would run the HIP kernel on these
+    inputs (GPU, bf16, D in {64,128}, Hq % Hkv == 0, T <= 16, d innermost
+    with 8-element-aligned strides, not disabled)."""
+    if os.environ.get("GENREC_DISABLE_ATTN_BEAM", "0") == "1":
+        return False
+    if not (q.dim() == 4 and k_pre.dim() == 4 and k_suf.dim() == 5
+            and anc.dim() == 3 and q.size(2) == 1):
+        return False
+    if not (q.dtype == k_pre.dtype == v_pre.dtype == k_suf.dtype
+            == v_suf.dtype == torch.bfloat16):
+        return False
+    B, Hkv, Lp, D = k_pre.shape
+    if D not in GQA_HEAD_DIMS or q.size(3) != D or v_pre.shape != k_pre.shape:
+        return False
+    if B == 0 or Lp == 0 or Hkv == 0 or q.size(1) % Hkv != 0 \
+            or q.size(0) == 0 or q.size(0) % B != 0:
+        return False
+    T, W = k_suf.size(1), q.size(0) // B
+    if tuple(k_suf.shape) != (B, T, W, Hkv, D) or v_suf.shape != k_suf.shape \
+            or tuple(anc.shape) != (B, W, T) or not 1 <= T <= BEAM_MAX_SUFFIX:
+        return False
+    if not (k_suf.is_contiguous() and v_suf.is_contiguous()):
+        return False
+    for x, dims in ((q, (0, 1)), (k_pre, (0, 1, 2)), (v_pre, (0, 1, 2))):
+        if x.stride(3) != 1 or any(x.stride(d) % 8 for d in dims) \
+                or x.data_ptr() % 16:
+            return False
+    return _kernel_available("beam_attn_fwd", q, k_pre, v_pre, k_suf, v_suf,
+                             anc)
+
+
+def beam_decode_attention(
+    q: Tensor,      # [B*W, Hq, 1, D]
+    k_pre: Tensor,  # [B, Hkv, Lp, D]   one copy per prompt
+    v_pre: Tensor,  # [B, Hkv, Lp, D]
+    k_suf: Tensor,  # [B, T, W, Hkv, D] slot s: what beam slot w wrote at step s
+    v_suf: Tensor,  # [B, T, W, Hkv, D]
+    anc: Tensor,    # [B, W, T] int: slot whose step-s K/V beam w inherits
+    t: int,         # suffix slots 0..t-1 are live
+    *,
+    pre_pad: Optional[Tensor] = None,  # [B, Lp] bool, True = PAD
+    scale: float,
+    _splits: int = 0,
+) -> Tensor:
+    """One beam-search decode step over a shared prompt prefix
+    -> [B*W, 1, Hq, D] (csrc/kernels/attention_beam.hip).
+
+    Beam (b, w) attends to prompt b's Lp prefix keys and to its own t
+    generated tokens, found through anc; no K/V is expanded or reordered.
+    Inputs the kernel does not cover materialise the per-beam K/V and go
+    through gqa_flash_attention. _splits (tests) fixes the prefix split
+    count; 0 picks it from the device's CU count.
+    """
+    if beam_decode_supported(q, k_pre, v_pre, k_suf, v_suf, anc):
+        from genrec_amd import ops
+
+        pad = None
+        if pre_pad is not None:
+            pad = pre_pad.to(torch.bool).contiguous()
+        return ops.ext().beam_attn_fwd(
+            q, k_pre, v_pre, pad, k_suf, v_suf,
+            anc.to(torch.int32).contiguous(), int(t), float(scale),
+            int(_splits))
+    if not q.is_cuda:
+        return eager.beam_decode_attention(q, k_pre, v_pre, k_suf, v_suf,
+                                           anc, t, pre_pad=pre_pad,
+                                           scale=scale)
+    k, v, key_pad = eager.beam_kv_expand(k_pre, v_pre, k_suf, v_suf, anc, t,
+                                         pre_pad)
+    return gqa_flash_attention(q, k, v, key_pad_mask=key_pad, scale=scale,
+                               causal=True)

@@ -134,6 +134,52 @@ def gqa_attention(
     return out.to(q.dtype)
 
 
+def beam_kv_expand(k_pre: Tensor, v_pre: Tensor, k_suf: Tensor,
+                   v_suf: Tensor, anc: Tensor, t: int,
+                   pre_pad: Optional[Tensor] = None):
+    """Per-beam K/V of a shared-prefix beam cache, materialised.
+
+    -> (k, v [B*W, Hkv, Lp+t, D], key_pad [B*W, Lp+t] bool | None): beam
+    (b, w) gets prompt b's prefix followed by k_suf[b, s, anc[b,w,s]] for
+    s < t. Slots s >= t of k_suf/v_suf/anc are never read.
+    """
+    B, T, W, Hkv, D = k_suf.shape
+    idx = anc[:, :, :t].long()[..., None, None].expand(B, W, t, Hkv, D)
+
+    def one(pre, suf):
+        # [B,T,W,Hkv,D] -> [B,slot,t,Hkv,D], pick slot anc[b,w,s] per (w,s)
+        own = suf[:, :t].permute(0, 2, 1, 3, 4).gather(1, idx)
+        own = own.reshape(B * W, t, Hkv, D).transpose(1, 2)
+        return torch.cat([pre.repeat_interleave(W, dim=0), own], dim=2)
+
+    key_pad = None
+    if pre_pad is not None:
+        key_pad = F.pad(pre_pad.bool().repeat_interleave(W, dim=0), (0, t),
+                        value=False)
+    return one(k_pre, k_suf), one(v_pre, v_suf), key_pad
+
+
+def beam_decode_attention(
+    q: Tensor,      # [B*W, Hq, 1, D]
+    k_pre: Tensor,  # [B, Hkv, Lp, D]
+    v_pre: Tensor,  # [B, Hkv, Lp, D]
+    k_suf: Tensor,  # [B, T, W, Hkv, D]
+    v_suf: Tensor,  # [B, T, W, Hkv, D]
+    anc: Tensor,    # [B, W, T] int
+    t: int,
+    *,
+    pre_pad: Optional[Tensor] = None,  # [B, Lp] bool, True = PAD
+    scale: float,
+) -> Tensor:
+    """One beam-search decode step over a shared prompt prefix, fp32 math
+    -> [B*W, 1, Hq, D]: each beam's suffix is gathered through anc, appended
+    to its prompt's prefix, and attended with gqa_attention (Lq = 1)."""
+    k, v, key_pad = beam_kv_expand(k_pre, v_pre, k_suf, v_suf, anc, t,
+                                   pre_pad)
+    return gqa_attention(q, k, v, key_pad_mask=key_pad, scale=scale,
+                         causal=True)
+
+
 def pairwise_sqdist(x: Tensor, codebook: Tensor) -> Tensor:
     """L2 distance matrix ||x||^2 + ||c||^2 - 2 x c^T (ref rqvae.py:186-192)."""
     return (

@@ -99,10 +99,12 @@ def extract_sem_ids(text: str, n_codebooks: int) -> Optional[List[int]]:
 @torch.no_grad()
 def evaluate_aux_tasks(model: LCRec, metas, device,
                        helper: ConstrainedDecodingHelper, n_codebooks: int,
-                       max_samples: int = 64) -> Dict[str, float]:
+                       max_samples: int = 64,
+                       beam_cache: Optional[str] = None) -> Dict[str, float]:
     """item2index greedy accuracy + index2item substring match
     (ref lcrec_trainer.py:190-222)."""
     from genrec_amd.data.lcrec_sft import TEMPLATES, sem_ids_to_tokens
+    from genrec_amd.ops.attention import BEAM_MAX_SUFFIX
 
     allowed = helper.allowed_token_ids()
     metas = metas[:max_samples]
@@ -120,7 +122,8 @@ def evaluate_aux_tasks(model: LCRec, metas, device,
                               attention_mask=batch["attention_mask"]
                               .to(device),
                               max_new_tokens=n_codebooks, beam_width=1,
-                              allowed_token_ids=allowed)
+                              allowed_token_ids=allowed,
+                              beam_cache=beam_cache)
     L = ids.size(1)
     for m, row in zip(metas, res):
         text = model.decode(row[0][0][L:], skip_special_tokens=False)
@@ -132,10 +135,15 @@ def evaluate_aux_tasks(model: LCRec, metas, device,
     batch = sft_collate([{"prompt": p, "response": ""} for p in prompts],
                         model, for_generation=True)
     ids = batch["input_ids"].to(device)
+    # free generation runs past the shared-prefix cache's suffix slots
+    # (and one beam has nothing to share): it keeps the default cache
+    free_len = 24
     res = model.generate_topk(ids,
                               attention_mask=batch["attention_mask"]
                               .to(device),
-                              max_new_tokens=24, beam_width=1)
+                              max_new_tokens=free_len, beam_width=1,
+                              beam_cache=beam_cache
+                              if free_len <= BEAM_MAX_SUFFIX else None)
     L = ids.size(1)
     for m, row in zip(metas, res):
         text = model.decode(row[0][0][L:], skip_special_tokens=True)
@@ -150,7 +158,8 @@ def evaluate(model: LCRec, loader, device, helper: ConstrainedDecodingHelper,
              n_codebooks: int, ks=(1, 5, 10), beam_width: int = 10,
              max_batches: Optional[int] = None,
              aux_tasks: bool = True,
-             debug_logging: bool = False) -> Dict[str, float]:
+             debug_logging: bool = False,
+             beam_cache: Optional[str] = None) -> Dict[str, float]:
     model.eval()
     acc = TopKAccumulator(ks=list(ks))
     allowed = helper.allowed_token_ids()
@@ -165,7 +174,8 @@ def evaluate(model: LCRec, loader, device, helper: ConstrainedDecodingHelper,
             aux_metas.extend(metas)
         res = model.generate_topk(
             ids, attention_mask=attn, max_new_tokens=n_codebooks,
-            beam_width=beam_width, allowed_token_ids=allowed)
+            beam_width=beam_width, allowed_token_ids=allowed,
+            beam_cache=beam_cache)
         L = ids.size(1)
         preds, tgts = [], []
         for b, row in enumerate(res):
@@ -188,7 +198,7 @@ def evaluate(model: LCRec, loader, device, helper: ConstrainedDecodingHelper,
     metrics = acc.reduce(all_reduce=True)
     if aux_tasks:
         aux = evaluate_aux_tasks(model, aux_metas, device, helper,
-                                 n_codebooks)
+                                 n_codebooks, beam_cache=beam_cache)
         aux = reduce_scalars(aux, device)
         t = max(aux.pop("aux_total"), 1.0)
         metrics["item2index_acc"] = aux["item2index_correct"] / t
@@ -246,6 +256,9 @@ def train(
     # None = the backbone's own loss; "genrec_lce" = chunked linear + CE
     # that never forms the [B*L, V] logits
     loss_implementation: Optional[str] = None,
+    # None = expanded, reordered KV cache in generate_topk; "shared_prefix"
+    # = one prompt copy + per-beam suffix slots (needs "genrec_gqa")
+    beam_cache: Optional[str] = None,
 ):
     if max_length is not None:
         max_seq_len = max_length
@@ -310,7 +323,8 @@ def train(
         metrics = evaluate(model, valid_loader, device, helper, n_codebooks,
                            beam_width=eval_beam_width,
                            max_batches=eval_max_batches,
-                           debug_logging=debug_logging)
+                           debug_logging=debug_logging,
+                           beam_cache=beam_cache)
         if ctx.is_main:
             logger.info("eval-only %s", metrics)
         wb.finish()
@@ -357,7 +371,8 @@ def train(
             metrics = evaluate(model, valid_loader, device, helper,
                                n_codebooks, beam_width=eval_beam_width,
                                max_batches=eval_max_batches,
-                               debug_logging=debug_logging)
+                               debug_logging=debug_logging,
+                               beam_cache=beam_cache)
             if ctx.is_main:
                 logger.info("epoch %d eval %s", epoch, metrics)
                 wb.log({f"eval/{k}": v for k, v in metrics.items()})

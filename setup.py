@@ -30,6 +30,7 @@ sources = [
     "csrc/kernels/adamw.hip",
     "csrc/kernels/attention_flash.hip",
     "csrc/kernels/attention_gqa.hip",
+    "csrc/kernels/attention_beam.hip",
     "csrc/kernels/skinny_gemm.hip",
 ]
 
@@ -42,7 +43,7 @@ if os.environ.get("GENREC_DEBUG_BUILD", "0") == "1":
     hip_flags = ["-O1", "-g", "-std=c++17", "-fno-omit-frame-pointer"]
 
 # The generated HIP compile rule tracks no header dependencies, so an edit
-# to a shared header (csrc/core/*.h holds the MFMA tile primitives of five
+# to a shared header (csrc/core/*.h holds the MFMA tile primitives of six
 # kernels) would leave stale objects. Put the headers' newest mtime on the
 # HIP command line: ninja rebuilds an object whose command changed.
 import glob

@@ -128,6 +128,25 @@ def build_cases():
         return ops.ext().gqa_attn_bwd(doutg, qg, kg, vg, go, glse, padg,
                                       sg, True)
 
+    # shared-prefix beam decode: 14 query heads on 2 KV heads x 10 beams =
+    # 70 packed rows (two Q tiles), three K tiles over 2 splits, left
+    # padding, 3 live suffix slots with a shared ancestor
+    Bb, Wb = 2, 10
+    qb = torch.randn(Bb * Wb, 1, 14, Dg, device=dev,
+                     dtype=torch.bfloat16).transpose(1, 2)
+    kb = torch.randn(Bb, Lg, 2, Dg, device=dev,
+                     dtype=torch.bfloat16).transpose(1, 2)
+    vb = torch.randn_like(kb)
+    ksb = torch.randn(Bb, 4, Wb, 2, Dg, device=dev, dtype=torch.bfloat16)
+    vsb = torch.randn_like(ksb)
+    ancb = torch.randint(0, Wb, (Bb, Wb, 4), device=dev, dtype=torch.int32)
+    ancb[:, 1] = ancb[:, 0]
+    padb = padg[:Bb]
+
+    def beam_fwd():
+        return ops.ext().beam_attn_fwd(qb, kb, vb, padb, ksb, vsb, ancb, 3,
+                                       sg, 2)
+
     x = torch.randn(4096, 384, device=dev, dtype=torch.bfloat16)
     w = torch.randn(384, device=dev, dtype=torch.bfloat16)
 
@@ -177,6 +196,7 @@ def build_cases():
         # no atomics anywhere: bitwise
         ("gqa_attn_fwd", gqa_fwd, 0.0),
         ("gqa_attn_bwd", gqa_bwd, 0.0),
+        ("beam_attn_fwd", beam_fwd, 0.0),
         ("rms_norm", rms, 0.0),
         ("layer_norm_fwd", ln_fwd, 0.0),
         ("layer_norm_bwd", ln_bwd, 0.0),
