@@ -40,7 +40,10 @@ std::vector<torch::Tensor> attn_bwd_mfma(
     c10::optional<torch::Tensor> query_mask,
     double scale, int64_t act, double dropout_p, int64_t seed,
     bool bias_grad, int64_t bias_dim,
-    c10::optional<torch::Tensor> bias_bucket, int64_t n_buckets);
+    c10::optional<torch::Tensor> bias_bucket, int64_t n_buckets,
+    c10::optional<torch::Tensor> dqkv_out);
+std::string attn_mfma_path(int64_t Lq, int64_t Lk, int64_t D, int64_t act,
+                           bool table_mode, bool backward);
 
 std::vector<torch::Tensor> hstu_attn_fwd(
     torch::Tensor q, torch::Tensor k, torch::Tensor v,
@@ -156,7 +159,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scale"), py::arg("act"), py::arg("dropout_p"),
         py::arg("seed"), py::arg("bias_grad"), py::arg("bias_dim"),
         py::arg("bias_bucket") = py::none(),
-        py::arg("n_buckets") = 0);
+        py::arg("n_buckets") = 0,
+        py::arg("dqkv_out") = py::none());
+  m.def("attn_mfma_path", &genrec::attn_mfma_path,
+        "kernel family attn_fwd_mfma (attn_bwd_mfma: backward=True) runs "
+        "for a shape: "
+        "\"smallq\" or \"tile64\"",
+        py::arg("Lq"), py::arg("Lk"), py::arg("D"), py::arg("act") = 0,
+        py::arg("table_mode") = false, py::arg("backward") = false);
   m.def("hstu_attn_fwd", &genrec::hstu_attn_fwd, "HSTU fused attention fwd");
   m.def("hstu_attn_bwd", &genrec::hstu_attn_bwd, "HSTU fused attention bwd");
   m.def("softmax_ce_fwd", &genrec::softmax_ce_fwd, "fused CE forward");

@@ -146,6 +146,22 @@ class T5Attention(nn.Module):
                     kv_cache["k"], kv_cache["v"] = k, v
         else:
             qkv = self.qkv(query)
+            table_bias = self.rel_bias is not None and \
+                os.environ.get("GENREC_ATTN_TABLE_BIAS", "0") == "1"
+            if ops.packed_qkv_eligible(qkv, self.n_heads, attn_mask,
+                                       kv_cache, table_bias):
+                # the attention backward writes the gradient of qkv as one
+                # tensor: no concatenation of dq, dk, dv
+                seq = qkv.size(1)
+                bias = None
+                if self.rel_bias is not None:
+                    bias = self.compute_bias(seq, seq, qkv.device)
+                out = ops.t5_self_attention_packed(
+                    qkv, self.n_heads, bias, key_padding_mask, attn_mask,
+                    self.scale, self.dropout_p, self.training)
+                out = out.transpose(1, 2).reshape(qkv.size(0), -1,
+                                                  self.d_model)
+                return self.o(out)
             q_flat, k, v = qkv.chunk(3, dim=-1)
             k, v = self._split(k), self._split(v)
             if kv_cache is not None:

@@ -82,6 +82,8 @@ from genrec_amd.ops.attention import (  # noqa: E402
     fused_attention,
     sasrec_attention,
     t5_attention,
+    t5_self_attention_packed,
+    packed_qkv_eligible,
     hstu_pointwise_attention,
     hstu_fused_attention,
     gqa_flash_attention,
@@ -110,6 +112,8 @@ __all__ = [
     "fused_attention",
     "sasrec_attention",
     "t5_attention",
+    "t5_self_attention_packed",
+    "packed_qkv_eligible",
     "hstu_pointwise_attention",
     "hstu_fused_attention",
     "gqa_flash_attention",

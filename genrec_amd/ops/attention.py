@@ -131,6 +131,113 @@ class _FusedAttnFn(torch.autograd.Function):
                 None, None, None, None, None, None, None, None)
 
 
+def _qkv_views(qkv: Tensor, n_heads: int):
+    """[B,H,L,D] q/k/v views of a fused [B,L,3*H*D] projection output: what
+    qkv.chunk(3, -1) followed by the head split and transpose gives."""
+    b, l, w = qkv.shape
+    parts = qkv.view(b, l, 3, n_heads, w // (3 * n_heads))
+    return (parts[:, :, 0].transpose(1, 2), parts[:, :, 1].transpose(1, 2),
+            parts[:, :, 2].transpose(1, 2))
+
+
+class _PackedSelfAttnFn(torch.autograd.Function):
+    """MFMA self-attention on the fused qkv projection output. Forward is
+    _FusedAttnFn's; backward has the kernel write dq/dk/dv straight into
+    the column blocks of ONE [B,L,3*H*D] gradient, so the concatenation
+    that chunk's backward would launch never runs."""
+
+    @staticmethod
+    def forward(ctx, qkv, n_heads, bias, key_pad_mask, additive_mask, scale,
+                dropout_p, training):
+        from genrec_amd import ops
+
+        qkv = qkv if qkv.is_contiguous() else qkv.contiguous()
+        q, k, v = _qkv_views(qkv, n_heads)
+        seed_dev = None
+        seed = 0
+        if dropout_p > 0 and training:
+            seed = _call_seed()
+            seed_dev = _seed_counter(qkv.device)
+        out, probs, dmask = ops.ext().attn_fwd_mfma(
+            q, k, v, bias, key_pad_mask, additive_mask, None,
+            scale, False, _ACT_SOFTMAX, dropout_p if training else 0.0, seed,
+            seed_dev,
+        )
+        ctx.save_for_backward(qkv, probs, dmask)
+        ctx.meta = (n_heads, scale, dropout_p if training else 0.0, seed,
+                    bias is not None and bias.requires_grad,
+                    bias.dim() if bias is not None else 0,
+                    bias.dtype if bias is not None else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from genrec_amd import ops
+
+        qkv, probs, dmask = ctx.saved_tensors
+        (n_heads, scale, dropout_p, seed, bias_grad, bias_dim,
+         bias_dtype) = ctx.meta
+        q, k, v = _qkv_views(qkv, n_heads)
+        if dout.stride(-1) != 1:
+            dout = dout.contiguous()
+        dqkv = torch.empty_like(qkv)
+        _, _, _, dbias = ops.ext().attn_bwd_mfma(
+            dout, q, k, v, probs, dmask, None,
+            scale, _ACT_SOFTMAX, dropout_p, seed, bias_grad, bias_dim,
+            None, 0, dqkv,
+        )
+        if bias_grad and dbias.dtype != bias_dtype:
+            dbias = dbias.to(bias_dtype)
+        return (dqkv, None, dbias if bias_grad else None,
+                None, None, None, None, None)
+
+
+def _packed_qkv_fits(qkv: Tensor, n_heads: int,
+                     additive_mask: Optional[Tensor], kv_cache: Optional[dict],
+                     table_bias: bool) -> bool:
+    """the conditions of packed_qkv_eligible that do not depend on the
+    device or on the environment"""
+    if kv_cache is not None or table_bias or qkv.dim() != 3:
+        return False
+    if qkv.dtype != torch.bfloat16 or qkv.size(2) % (3 * n_heads) != 0:
+        return False
+    d = qkv.size(2) // (3 * n_heads)
+    if d % 32 != 0 or d > 64 or qkv.size(1) > 64 or qkv.size(1) < 1:
+        return False
+    return additive_mask is None or additive_mask.dim() == 2
+
+
+def packed_qkv_eligible(qkv: Tensor, n_heads: int,
+                        additive_mask: Optional[Tensor] = None,
+                        kv_cache: Optional[dict] = None,
+                        table_bias: bool = False) -> bool:
+    """True iff t5_self_attention_packed would run the MFMA kernels on this
+    fused [B,L,3*H*D] projection output: no kv_cache, bf16 on the GPU,
+    D % 32 == 0, D <= 64, L <= 64, a 2-D additive mask or none, dense bias
+    mode, and none of the knobs that route attention elsewhere."""
+    if not _packed_qkv_fits(qkv, n_heads, additive_mask, kv_cache,
+                            table_bias) or not qkv.is_cuda:
+        return False
+    for knob in ("GENREC_DISABLE_PACKED_QKV", "GENREC_DISABLE_ATTN",
+                 "GENREC_FORCE_FLASH", "GENREC_DISABLE_MFMA"):
+        if os.environ.get(knob, "0") == "1":
+            return False
+    return _kernel_available("attn_fwd_mfma", qkv)
+
+
+def t5_self_attention_packed(qkv, n_heads, bias, key_pad_mask, additive_mask,
+                             scale, dropout_p, training):
+    """T5 self-attention on the fused projection output qkv [B,L,3*H*D]
+    -> [B,H,L,D]. The caller checks packed_qkv_eligible first. Computes
+    what t5_attention computes on the chunked views; the gradient of qkv
+    comes back as one tensor."""
+    b = bias.contiguous() if bias is not None else None
+    kp = key_pad_mask.contiguous() if key_pad_mask is not None else None
+    am = additive_mask.contiguous() if additive_mask is not None else None
+    return _PackedSelfAttnFn.apply(qkv, n_heads, b, kp, am, scale, dropout_p,
+                                   training)
+
+
 class _FusedAttnTableBiasFn(torch.autograd.Function):
     """MFMA attention with the rel-bias TABLE gathered in-kernel
     (HSTU-style; round 2): no materialized [H,Lq,Lk] bias tensor in
