@@ -41,7 +41,8 @@ std::vector<torch::Tensor> attn_bwd_mfma(
     double scale, int64_t act, double dropout_p, int64_t seed,
     bool bias_grad, int64_t bias_dim,
     c10::optional<torch::Tensor> bias_bucket, int64_t n_buckets,
-    c10::optional<torch::Tensor> dqkv_out);
+    c10::optional<torch::Tensor> dqkv_out,
+    c10::optional<torch::Tensor> dkv_out, int64_t dk_col, int64_t dv_col);
 std::string attn_mfma_path(int64_t Lq, int64_t Lk, int64_t D, int64_t act,
                            bool table_mode, bool backward);
 
@@ -85,6 +86,7 @@ std::vector<torch::Tensor> plain_dropout_fwd(
     c10::optional<torch::Tensor> seed_dev);
 torch::Tensor colsum(torch::Tensor x);
 torch::Tensor chunk_sum(torch::Tensor x);
+torch::Tensor seq_sum_bf16(torch::Tensor x, bool reverse);
 std::vector<torch::Tensor> layer_norm_fwd(torch::Tensor x, torch::Tensor w,
                                           torch::Tensor b, double eps);
 std::vector<torch::Tensor> layer_norm_bwd(torch::Tensor dy, torch::Tensor x,
@@ -160,7 +162,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("seed"), py::arg("bias_grad"), py::arg("bias_dim"),
         py::arg("bias_bucket") = py::none(),
         py::arg("n_buckets") = 0,
-        py::arg("dqkv_out") = py::none());
+        py::arg("dqkv_out") = py::none(),
+        py::arg("dkv_out") = py::none(), py::arg("dk_col") = 0,
+        py::arg("dv_col") = 0);
   m.def("attn_mfma_path", &genrec::attn_mfma_path,
         "kernel family attn_fwd_mfma (attn_bwd_mfma: backward=True) runs "
         "for a shape: "
@@ -186,6 +190,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "graph-replay-safe plain dropout fwd");
   m.def("colsum", &genrec::colsum,
         "deterministic replay-safe column sum (bias grads)");
+  m.def("seq_sum_bf16", &genrec::seq_sum_bf16,
+        "row sum in the given order, every partial sum rounded to bf16",
+        py::arg("x"), py::arg("reverse") = false);
   m.def("chunk_sum", &genrec::chunk_sum,
         "small-row-count column sum (split-K dW partials)");
   m.def("layer_norm_fwd", &genrec::layer_norm_fwd, "fused LayerNorm fwd");

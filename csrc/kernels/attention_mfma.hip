@@ -1275,7 +1275,8 @@ std::vector<torch::Tensor> attn_bwd_mfma(
     double scale, int64_t act, double dropout_p, int64_t seed,
     bool bias_grad, int64_t bias_dim,
     c10::optional<torch::Tensor> bias_bucket, int64_t n_buckets,
-    c10::optional<torch::Tensor> dqkv_out) {
+    c10::optional<torch::Tensor> dqkv_out,
+    c10::optional<torch::Tensor> dkv_out, int64_t dk_col, int64_t dv_col) {
   (void)seed;
   const int B = q.size(0), H = q.size(1), Lq = q.size(2), D = q.size(3);
   const int Lk = k.size(2);
@@ -1283,8 +1284,48 @@ std::vector<torch::Tensor> attn_bwd_mfma(
   TORCH_CHECK(dout.stride(3) == 1 && q.stride(3) == 1 && k.stride(3) == 1 &&
                   v.stride(3) == 1,
               "attn_bwd_mfma: innermost (D) stride must be 1");
+  TORCH_CHECK(!(dqkv_out.has_value() && dkv_out.has_value()),
+              "attn_bwd_mfma: dqkv_out and dkv_out are mutually exclusive");
   torch::Tensor dq, dk, dv;
-  if (dqkv_out.has_value()) {
+  if (dkv_out.has_value()) {
+    // packed cross-attention gradient: dk and dv are [B,H,Lk,D] views of
+    // two H*D-wide column blocks (at element columns dk_col and dv_col) of
+    // one [B,Lk,W] buffer that several calls share — each call fills its
+    // own blocks, so the K/V projections of all decoder layers get their
+    // output gradient as one tensor. dq stays a fresh tensor; Lq != Lk is
+    // fine. The kernels store dK/dV element by element through the
+    // strides, so a row stride of W and a column offset need no alignment
+    // beyond the element's own.
+    const int64_t HD = (int64_t)H * D;
+    TORCH_CHECK(dkv_out->scalar_type() == torch::kBFloat16,
+                "attn_bwd_mfma: dkv_out must be bf16");
+    TORCH_CHECK(q.scalar_type() == torch::kBFloat16 &&
+                    k.scalar_type() == torch::kBFloat16 &&
+                    v.scalar_type() == torch::kBFloat16,
+                "attn_bwd_mfma: dkv_out needs bf16 q/k/v");
+    TORCH_CHECK(dkv_out->is_contiguous() && dkv_out->dim() == 3,
+                "attn_bwd_mfma: dkv_out must be a contiguous [B, Lk, W] "
+                "tensor");
+    TORCH_CHECK(dkv_out->device() == q.device(),
+                "attn_bwd_mfma: dkv_out must be on the device of q");
+    TORCH_CHECK(k.size(0) == B && k.size(1) == H && k.size(3) == D &&
+                    v.sizes() == k.sizes(),
+                "attn_bwd_mfma: k/v must be [B, H, Lk, D]");
+    const int64_t W = dkv_out->size(2);
+    TORCH_CHECK(dkv_out->size(0) == B && dkv_out->size(1) == Lk &&
+                    W >= 2 * HD && W % HD == 0,
+                "attn_bwd_mfma: dkv_out must be [B, Lk, n_blocks*H*D] with "
+                "n_blocks >= 2");
+    TORCH_CHECK(dk_col >= 0 && dv_col >= 0 && dk_col % HD == 0 &&
+                    dv_col % HD == 0 && dk_col + HD <= W &&
+                    dv_col + HD <= W && dk_col != dv_col,
+                "attn_bwd_mfma: dk_col/dv_col must be distinct multiples of "
+                "H*D inside dkv_out's last dimension");
+    auto blocks = dkv_out->view({B, Lk, W / HD, H, D});
+    dq = torch::empty_like(q);
+    dk = blocks.select(2, dk_col / HD).transpose(1, 2);
+    dv = blocks.select(2, dv_col / HD).transpose(1, 2);
+  } else if (dqkv_out.has_value()) {
     // packed self-attention gradient: dq/dk/dv are [B,H,L,D] views of the
     // three column blocks of one [B,L,3*H*D] buffer, which is the layout
     // the fused qkv projection's backward reads — the kernels write

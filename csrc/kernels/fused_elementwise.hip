@@ -187,6 +187,52 @@ torch::Tensor chunk_sum(torch::Tensor x) {
   return out;
 }
 
+// out[j] = (((x[r0, j] + x[r1, j]) + x[r2, j]) + ...) over the rows in
+// the order given (last row first when `reverse`), every partial sum
+// rounded to bf16: what a chain of bf16 tensor adds (fp32 add, one
+// rounding each) gives, in one pass over the rows instead of one per add.
+// The fused cross-attention K/V projection uses it to sum the layers'
+// input gradients exactly as autograd accumulates them on the per-layer
+// route. One thread per column quad, 8-byte loads.
+__global__ void seq_sum_bf16_kernel(const uint2* __restrict__ x,
+                                    uint2* __restrict__ out, int rows,
+                                    int64_t cols4, bool reverse) {
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < cols4;
+       q += (int64_t)gridDim.x * blockDim.x) {
+    BF16x4 acc;
+    acc.u = x[(int64_t)(reverse ? rows - 1 : 0) * cols4 + q];
+    for (int i = 1; i < rows; ++i) {
+      const int r = reverse ? rows - 1 - i : i;
+      BF16x4 v;
+      v.u = x[(int64_t)r * cols4 + q];
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        acc.e[k] = from_f32<__hip_bfloat16>(to_f32(acc.e[k]) + to_f32(v.e[k]));
+    }
+    out[q] = acc.u;
+  }
+}
+
+torch::Tensor seq_sum_bf16(torch::Tensor x, bool reverse) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2 &&
+                  x.scalar_type() == torch::kBFloat16,
+              "seq_sum_bf16: 2D contiguous cuda bf16 tensor required");
+  const int64_t rows = x.size(0), cols = x.size(1);
+  TORCH_CHECK((cols & 3) == 0 && rows >= 1 && rows <= 65536,
+              "seq_sum_bf16: cols %% 4 != 0 or bad row count");
+  auto out = torch::empty({cols}, x.options());
+  const int64_t cols4 = cols >> 2;
+  if (cols4 == 0) return out;
+  dim3 block(256);
+  dim3 grid((unsigned)std::min<int64_t>((cols4 + 255) / 256, 16384));
+  hipLaunchKernelGGL(seq_sum_bf16_kernel, grid, block, 0,
+                     at::cuda::getCurrentHIPStream(),
+                     reinterpret_cast<const uint2*>(x.data_ptr()),
+                     reinterpret_cast<uint2*>(out.data_ptr()), (int)rows,
+                     cols4, reverse);
+  return out;
+}
+
 // mask bits: bit0 = dropout keep, bit1 = relu pass (x > 0)
 template <typename T, bool RELU>
 __global__ void dropout_fuse_bwd_kernel(const T* __restrict__ dy,

@@ -136,8 +136,21 @@ class T5Attention(nn.Module):
                 value: Optional[Tensor] = None,
                 attn_mask: Optional[Tensor] = None,
                 key_padding_mask: Optional[Tensor] = None,
-                kv_cache: Optional[dict] = None) -> Tensor:
+                kv_cache: Optional[dict] = None,
+                cross_kv: Optional[tuple] = None) -> Tensor:
+        """cross_kv = (CrossKV, layer index): a cross-attention layer then
+        takes its K/V from the stack's one fused projection of the memory
+        (ops.project_cross_kv) and leaves self.k / self.v to it."""
         if self.is_cross_attention:
+            if cross_kv is not None:
+                ckv, layer = cross_kv
+                q = self._split(self.q(query))
+                out = ops.cross_attention_kv(
+                    q, ckv, layer, key_padding_mask, self.scale,
+                    self.dropout_p, self.training)
+                out = out.transpose(1, 2).reshape(q.size(0), -1,
+                                                  self.d_model)
+                return self.o(out)
             if kv_cache is not None and "k" in kv_cache:
                 k, v = kv_cache["k"], kv_cache["v"]
             else:
@@ -260,11 +273,13 @@ class TransformerBlock(nn.Module):
                 memory_key_padding_mask: Optional[Tensor] = None,
                 kv_cache: Optional[dict] = None,
                 normed: Optional[Tensor] = None,
-                next_norm: Optional[nn.Module] = None):
-        """Returns the block output. The two last arguments let a stack
+                next_norm: Optional[nn.Module] = None,
+                cross_kv: Optional[tuple] = None):
+        """Returns the block output. `normed` and `next_norm` let a stack
         fuse across blocks: `normed` is norm1(x) already computed by the
         previous block, and with `next_norm` (the next block's norm1) the
-        block returns (output, next_norm(output))."""
+        block returns (output, next_norm(output)). `cross_kv` goes to the
+        cross-attention layer (T5Attention.forward)."""
         self_cache = cross_cache = None
         if kv_cache is not None:
             self_cache = kv_cache.setdefault("self", {})
@@ -281,6 +296,7 @@ class TransformerBlock(nn.Module):
             x, normed = _dropout_add_norm(self.cross_attn(
                 normed, key=context, value=context,
                 key_padding_mask=memory_key_padding_mask, kv_cache=cross_cache,
+                cross_kv=cross_kv,
             ), x, self.dropout_cross.p, self.training, self.norm2)
         y = self.ff(normed)
         if next_norm is None:
@@ -304,13 +320,16 @@ def _dropout_add_norm(y: Tensor, x: Tensor, p: float, training: bool,
 
 
 def _run_layers(layers, x: Tensor, kv_caches: Optional[list] = None,
-                **kwargs) -> Tensor:
+                cross_kv=None, **kwargs) -> Tensor:
     """Run a stack of blocks, handing each block's last residual add to the
-    next block's norm1 so the pair runs fused."""
+    next block's norm1 so the pair runs fused. With `cross_kv` (a CrossKV)
+    block i gets (cross_kv, i)."""
     normed = None
     last = len(layers) - 1
     for i, layer in enumerate(layers):
         kv = kv_caches[i] if kv_caches is not None else None
+        if cross_kv is not None:
+            kwargs["cross_kv"] = (cross_kv, i)
         if i < last:
             x, normed = layer(x, kv_cache=kv, normed=normed,
                               next_norm=layers[i + 1].norm1, **kwargs)
@@ -351,8 +370,28 @@ class TransformerDecoder(nn.Module):
                 attn_mask: Optional[Tensor] = None,
                 key_padding_mask: Optional[Tensor] = None,
                 memory_key_padding_mask: Optional[Tensor] = None,
-                kv_caches: Optional[list] = None) -> Tensor:
-        return _run_layers(self.layers, tgt, kv_caches, context=memory,
+                kv_caches: Optional[list] = None,
+                cross_kv_impl: Optional[str] = None) -> Tensor:
+        """When the stack is eligible (ops.cross_kv_eligible: training-
+        style call without kv_caches, bf16 on the GPU, ...) the memory is
+        projected to every layer's cross-attention K/V in one GEMM;
+        GENREC_DISABLE_CROSS_KV_FUSE=1 keeps the per-layer projections.
+        cross_kv_impl="torch" (tests) takes the fused route in plain
+        PyTorch on any device and dtype."""
+        if cross_kv_impl is not None and kv_caches is not None:
+            raise ValueError("cross_kv_impl and kv_caches exclude each other")
+        cross_kv = None
+        attns = [layer.cross_attn for layer in self.layers]
+        if cross_kv_impl is not None or (attns and ops.cross_kv_eligible(
+                memory, tgt, [a.k.weight for a in attns],
+                [a.v.weight for a in attns],
+                [b for a in attns for b in (a.k.bias, a.v.bias)],
+                attns[0].n_heads, kv_caches)):
+            cross_kv = ops.project_cross_kv(
+                memory, [a.k.weight for a in attns],
+                [a.v.weight for a in attns], impl=cross_kv_impl)
+        return _run_layers(self.layers, tgt, kv_caches, cross_kv,
+                           context=memory,
                            attn_mask=attn_mask,
                            key_padding_mask=key_padding_mask,
                            memory_key_padding_mask=memory_key_padding_mask)

@@ -90,6 +90,9 @@ from genrec_amd.ops.attention import (  # noqa: E402
     beam_decode_attention,
     beam_decode_supported,
 )
+from genrec_amd.ops.cross_kv import (  # noqa: E402
+    cross_attention_kv, cross_kv_eligible, project_cross_kv,
+)
 from genrec_amd.ops.quantize import residual_quantize_step  # noqa: E402
 from genrec_amd.ops.losses import (  # noqa: E402
     softmax_ce, tied_softmax_ce, summed_ce, linear_cross_entropy,
@@ -119,6 +122,9 @@ __all__ = [
     "gqa_flash_attention",
     "beam_decode_attention",
     "beam_decode_supported",
+    "project_cross_kv",
+    "cross_attention_kv",
+    "cross_kv_eligible",
     "residual_quantize_step",
     "softmax_ce",
     "tied_softmax_ce",

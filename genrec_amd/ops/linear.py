@@ -89,6 +89,36 @@ def _use_skinny_dx(dy: torch.Tensor, weight: torch.Tensor) -> bool:
     return ops.has_ext()
 
 
+def splitk_grad_weight(dy2: torch.Tensor, x2: torch.Tensor,
+                       dtype: torch.dtype) -> torch.Tensor:
+    """dW = dy2^T x2 for dy2 [K, N], x2 [K, M] -> [N, M] in `dtype`: the
+    chunked bmm + fp32-accumulated chunk reduce when K is large and
+    divisible, the plain GEMM otherwise."""
+    k = x2.shape[0]
+    nc = _pick_chunks(k) if k >= _SPLITK_MIN_K else 1
+    if nc > 1 and x2.is_contiguous() and dy2.is_contiguous():
+        part = torch.bmm(
+            dy2.view(nc, k // nc, -1).transpose(1, 2),
+            x2.view(nc, k // nc, -1))
+        # fp32-accumulated chunk reduce. GENREC_CHUNK_SUM=1 swaps
+        # ATen's sum(0) for the genrec chunk_sum kernel — BITWISE
+        # identical (both accumulate bf16 in fp32, same row
+        # order) but measured perf-NEUTRAL on the TIGER bench
+        # (49.0k vs 48.9k same-box): the ~6 us per-dispatch
+        # average rocprof shows for ATen's reduce is launch-ramp
+        # inflation, not stream time. Opt-in, same policy as the
+        # skinny GEMM.
+        from genrec_amd import ops
+
+        n_el = part.shape[1] * part.shape[2]
+        if part.is_cuda and ops.has_ext() and n_el % 4 == 0 \
+                and os.environ.get("GENREC_CHUNK_SUM") == "1":
+            return ops.ext().chunk_sum(part.view(nc, n_el)) \
+                .view(part.shape[1], part.shape[2]).to(dtype)
+        return part.sum(0).to(dtype)
+    return dy2.t().matmul(x2).to(dtype)
+
+
 class _SplitKLinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: torch.Tensor, weight: torch.Tensor,
@@ -130,34 +160,9 @@ class _SplitKLinearFn(torch.autograd.Function):
                 dx = dy.matmul(weight.to(dy.dtype))
         dw = None
         if ctx.needs_input_grad[1]:
-            x2 = x.reshape(-1, x.shape[-1]).to(dy.dtype)
-            dy2 = dy.reshape(-1, dy.shape[-1])
-            k = x2.shape[0]
-            nc = _pick_chunks(k) if k >= _SPLITK_MIN_K else 1
-            if nc > 1 and x2.is_contiguous() and dy2.is_contiguous():
-                part = torch.bmm(
-                    dy2.view(nc, k // nc, -1).transpose(1, 2),
-                    x2.view(nc, k // nc, -1))
-                # fp32-accumulated chunk reduce. GENREC_CHUNK_SUM=1 swaps
-                # ATen's sum(0) for the genrec chunk_sum kernel — BITWISE
-                # identical (both accumulate bf16 in fp32, same row
-                # order) but measured perf-NEUTRAL on the TIGER bench
-                # (49.0k vs 48.9k same-box): the ~6 us per-dispatch
-                # average rocprof shows for ATen's reduce is launch-ramp
-                # inflation, not stream time. Opt-in, same policy as the
-                # skinny GEMM.
-                from genrec_amd import ops
-
-                n_el = part.shape[1] * part.shape[2]
-                if part.is_cuda and ops.has_ext() and n_el % 4 == 0 \
-                        and os.environ.get("GENREC_CHUNK_SUM") == "1":
-                    dw = ops.ext().chunk_sum(part.view(nc, n_el)) \
-                        .view(part.shape[1], part.shape[2]) \
-                        .to(weight.dtype)
-                else:
-                    dw = part.sum(0).to(weight.dtype)
-            else:
-                dw = dy2.t().matmul(x2).to(weight.dtype)
+            dw = splitk_grad_weight(dy.reshape(-1, dy.shape[-1]),
+                                    x.reshape(-1, x.shape[-1]).to(dy.dtype),
+                                    weight.dtype)
         db = None
         if ctx.has_bias and ctx.needs_input_grad[2]:
             dy2b = dy.reshape(-1, dy.shape[-1])
