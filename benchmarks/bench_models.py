@@ -134,11 +134,12 @@ def bench_rqvae(device, steps, warmup):
 
 def bench_lcrec(device, steps, warmup, full_size=False, attn_impl="sdpa",
                 loss_impl="hf", vocab=None, response_tokens=None,
-                eager_step=False):
+                eager_step=False, layer_impl="hf"):
     """LCRec SFT step: Qwen2-1.5B-shaped backbone (lcrec/amazon/lcrec.gin:
     B=32, L=512, bf16, grad ckpt) — full size only on GPU. attn_impl selects
     the backbone attention ("sdpa" | "genrec_gqa") and loss_impl the loss
-    ("hf" = the backbone's own | "genrec_lce") for same-box A/Bs. `vocab`
+    ("hf" = the backbone's own | "genrec_lce") and layer_impl the decoder
+    layer ("hf" = transformers' | "genrec_fused") for same-box A/Bs. `vocab`
     widens the head to a real tokenizer's size (the offline tokenizer is
     tiny); `response_tokens` supervises only the last K positions of each
     sample, as sft_collate does (default: every position, as before).
@@ -156,7 +157,9 @@ def bench_lcrec(device, steps, warmup, full_size=False, attn_impl="sdpa",
         cfg.vocab_size = vocab
     model = LCRec(config=cfg, attn_implementation=attn_impl,
                   loss_implementation=None if loss_impl == "hf"
-                  else loss_impl)
+                  else loss_impl,
+                  layer_implementation=None if layer_impl == "hf"
+                  else layer_impl)
     model.add_codebook_tokens(5, 256)
     if vocab is not None:
         # add_codebook_tokens resized to the offline tokenizer's length
@@ -189,7 +192,7 @@ def bench_lcrec(device, steps, warmup, full_size=False, attn_impl="sdpa",
     peak = torch.cuda.max_memory_allocated(device) / 2**30 \
         if device.type == "cuda" else None
     return dict(model="lcrec-qwen2-1.5b" if full_size else "lcrec-tiny",
-                attn=attn_impl, loss=loss_impl, vocab=V,
+                attn=attn_impl, loss=loss_impl, layers=layer_impl, vocab=V,
                 step="eager" if eager_step else "graph",
                 supervised_per_sample=response_tokens or L,
                 batch=B, seq_len=L, samples_per_s=B * steps / el,
@@ -238,6 +241,8 @@ def main():
                    default="sdpa")
     p.add_argument("--lcrec-loss", choices=["hf", "genrec_lce"],
                    default="hf")
+    p.add_argument("--lcrec-layers", choices=["hf", "genrec_fused"],
+                   default="hf")
     p.add_argument("--lcrec-vocab", type=int, default=None,
                    help="backbone vocabulary before the codebook tokens "
                         "(Qwen2.5: 151936)")
@@ -257,6 +262,7 @@ def main():
             kw["full_size"] = args.lcrec_full
             kw["attn_impl"] = args.lcrec_attn
             kw["loss_impl"] = args.lcrec_loss
+            kw["layer_impl"] = args.lcrec_layers
             kw["vocab"] = args.lcrec_vocab
             kw["response_tokens"] = args.lcrec_response_tokens
             kw["eager_step"] = args.lcrec_eager

@@ -140,6 +140,20 @@ torch::Tensor beam_attn_fwd(torch::Tensor q, torch::Tensor k_pre,
 int64_t beam_attn_pick_splits(int64_t B, int64_t Hkv, int64_t rows,
                               int64_t Lp);
 
+
+std::vector<torch::Tensor> add_rms_norm_fwd(
+    torch::Tensor x, c10::optional<torch::Tensor> residual, torch::Tensor w,
+    double eps);
+std::vector<torch::Tensor> add_rms_norm_bwd(
+    torch::Tensor dn, c10::optional<torch::Tensor> dh, torch::Tensor h,
+    torch::Tensor w, torch::Tensor inv_rms);
+std::vector<torch::Tensor> rope_qk_fwd(torch::Tensor q, torch::Tensor k,
+                                       torch::Tensor cos, torch::Tensor sin,
+                                       bool inverse);
+torch::Tensor swiglu_fwd(torch::Tensor gate, torch::Tensor up);
+std::vector<torch::Tensor> swiglu_bwd(torch::Tensor dy, torch::Tensor gate,
+                                      torch::Tensor up);
+
 }  // namespace genrec
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -224,4 +238,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scale"), py::arg("splits") = 0);
   m.def("beam_attn_pick_splits", &genrec::beam_attn_pick_splits,
         "prefix splits chosen for (B, Hkv, W*g rows, Lp)");
+  m.def("add_rms_norm_fwd", &genrec::add_rms_norm_fwd,
+        "wide-row (d <= 4096) residual add + RMSNorm fwd -> (h, n, inv_rms)",
+        py::arg("x"), py::arg("residual"), py::arg("w"), py::arg("eps"));
+  m.def("add_rms_norm_bwd", &genrec::add_rms_norm_bwd,
+        "RMSNorm bwd + dh add in one pass (deterministic dw) -> (dx, dw)",
+        py::arg("dn"), py::arg("dh"), py::arg("h"), py::arg("w"),
+        py::arg("inv_rms"));
+  m.def("rope_qk_fwd", &genrec::rope_qk_fwd,
+        "rotary embedding of q and k in one launch (inverse = gradient) -> "
+        "(q_out, k_out) as [B,H,L,D] views of [B,L,H,D] memory",
+        py::arg("q"), py::arg("k"), py::arg("cos"), py::arg("sin"),
+        py::arg("inverse") = false);
+  m.def("swiglu_fwd", &genrec::swiglu_fwd, "silu(gate) * up");
+  m.def("swiglu_bwd", &genrec::swiglu_bwd,
+        "silu(gate) * up backward, recomputed -> (dgate, dup)");
 }

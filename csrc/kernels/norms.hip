@@ -1012,9 +1012,9 @@ static int rms_bwd_block_cap() {
 }
 
 // dw = column sum of the [n_blocks, d] fp32 partials, cast to w's dtype
-static torch::Tensor rms_dw_finish(const torch::Tensor& dw, int n_blocks,
-                                   int d, const torch::Tensor& w,
-                                   hipStream_t stream) {
+// (also finishes llm_layer.hip's add_rms_norm_bwd partials)
+torch::Tensor rms_dw_finish(const torch::Tensor& dw, int n_blocks, int d,
+                            const torch::Tensor& w, hipStream_t stream) {
   auto dw_out = torch::empty({(int64_t)d}, w.options());
   int ch = 32;
   while ((int64_t)ch * d < 131072 && ch < 512 && ch * 4 < n_blocks) ch *= 2;

@@ -61,7 +61,25 @@ def _attn_kwargs(attn_implementation: Optional[str]) -> Dict[str, str]:
 
 
 LOSS_IMPLEMENTATIONS = (None, "genrec_lce")
+LAYER_IMPLEMENTATIONS = (None, "genrec_fused")
 BEAM_CACHES = (None, "shared_prefix")
+
+
+def _check_layer_implementation(layer_implementation: Optional[str]) -> None:
+    if layer_implementation not in LAYER_IMPLEMENTATIONS:
+        raise ValueError(
+            f"layer_implementation {layer_implementation!r}: expected one "
+            f"of {LAYER_IMPLEMENTATIONS}")
+
+
+def _apply_layer_implementation(model: nn.Module,
+                                layer_implementation: Optional[str]) -> None:
+    """None leaves the transformers layers alone; "genrec_fused" switches
+    this model instance's Qwen2 layers to genrec_amd.modules.hf_layers."""
+    if layer_implementation == "genrec_fused":
+        from genrec_amd.modules import hf_layers
+
+        hf_layers.install(model)
 
 
 @ginlite.configurable(name="LCRec")
@@ -69,9 +87,15 @@ class LCRec(nn.Module):
     def __init__(self, pretrained_path: Optional[str] = None,
                  config=None,
                  attn_implementation: Optional[str] = None,
-                 loss_implementation: Optional[str] = None) -> None:
+                 loss_implementation: Optional[str] = None,
+                 layer_implementation: Optional[str] = None) -> None:
         super().__init__()
         from transformers import AutoModelForCausalLM, AutoTokenizer
+
+        _check_layer_implementation(layer_implementation)
+        # None = the transformers decoder layer; "genrec_fused" = fused
+        # add+RMSNorm, RoPE and SwiGLU kernels inside every layer
+        self.layer_implementation = layer_implementation
 
         if loss_implementation not in LOSS_IMPLEMENTATIONS:
             raise ValueError(
@@ -96,6 +120,7 @@ class LCRec(nn.Module):
             if cfg.vocab_size < len(self.tokenizer):
                 cfg.vocab_size = len(self.tokenizer)
             self.model = AutoModelForCausalLM.from_config(cfg, **attn_kw)
+        _apply_layer_implementation(self.model, layer_implementation)
 
     def gradient_checkpointing_enable(self):
         self.model.gradient_checkpointing_enable()
@@ -190,6 +215,7 @@ class LCRec(nn.Module):
         self.model = AutoModelForCausalLM.from_pretrained(
             load_dir, torch_dtype=torch.bfloat16,
             **_attn_kwargs(self.attn_implementation))
+        _apply_layer_implementation(self.model, self.layer_implementation)
         logger.info("Loaded checkpoint from %s", load_dir)
 
     @torch.no_grad()

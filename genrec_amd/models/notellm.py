@@ -55,11 +55,20 @@ class Query2Embedding(nn.Module):
                  eos_token: str = "<|endoftext|>",
                  gradient_checkpointing: bool = True, tau: float = 3.0,
                  alpha: float = 0.01, hardneg_r: float = 0.1,
-                 attn_implementation: Optional[str] = None) -> None:
+                 attn_implementation: Optional[str] = None,
+                 layer_implementation: Optional[str] = None) -> None:
         super().__init__()
         # None keeps the transformers default; "genrec_gqa" routes the
         # Qwen2 layers through the project's grouped-query flash kernel
-        from genrec_amd.models.lcrec import _attn_kwargs
+        from genrec_amd.models.lcrec import (
+            _apply_layer_implementation, _attn_kwargs,
+            _check_layer_implementation,
+        )
+
+        # None = the transformers decoder layer; "genrec_fused" = fused
+        # add+RMSNorm, RoPE and SwiGLU kernels inside every layer
+        _check_layer_implementation(layer_implementation)
+        self.layer_implementation = layer_implementation
 
         attn_kw = _attn_kwargs(attn_implementation)
         self.tau = nn.Parameter(torch.tensor(tau))
@@ -82,6 +91,7 @@ class Query2Embedding(nn.Module):
             cfg = config or default_qwen_config(
                 vocab_size=max(len(self.tokenizer) + 8, 512))
             self.model = AutoModelForCausalLM.from_config(cfg, **attn_kw)
+        _apply_layer_implementation(self.model, layer_implementation)
         if freeze_lm:
             for p in self.model.parameters():
                 p.requires_grad = False

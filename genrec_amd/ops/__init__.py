@@ -102,6 +102,7 @@ from genrec_amd.ops.embedding import embedding  # noqa: E402
 from genrec_amd.ops.fused import (  # noqa: E402
     dropout_add, dropout_add_rms_norm, plain_dropout, relu_dropout,
 )
+from genrec_amd.ops.llm_layer import add_rms_norm, rope_qk, swiglu  # noqa: E402
 
 __all__ = [
     "ext",
@@ -136,4 +137,7 @@ __all__ = [
     "dropout_add_rms_norm",
     "plain_dropout",
     "relu_dropout",
+    "add_rms_norm",
+    "rope_qk",
+    "swiglu",
 ]

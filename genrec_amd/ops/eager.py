@@ -374,3 +374,40 @@ def linear_cross_entropy(hidden: Tensor, weight: Tensor, targets: Tensor,
         hidden.reshape(-1, hidden.size(-1)).contiguous(), weight.contiguous(),
         targets.reshape(-1).contiguous(), ignore_index, reduction,
         chunk_rows, compact, torch.is_grad_enabled())
+
+
+# ---- Qwen2 decoder-layer pieces (ops/llm_layer.py): the stock transformers
+# op sequences, same ops in the same order, so the CPU path is the stock
+# model bit for bit.
+
+def add_rms_norm(x: Tensor, residual: Optional[Tensor], weight: Tensor,
+                 eps: float) -> tuple[Tensor, Tensor]:
+    """(h, n): h = x + residual (x itself without one), n = Qwen2RMSNorm(h)
+    (transformers modeling_qwen2.Qwen2RMSNorm.forward)."""
+    h = x if residual is None else x + residual
+    input_dtype = h.dtype
+    hf = h.to(torch.float32)
+    variance = hf.pow(2).mean(-1, keepdim=True)
+    hf = hf * torch.rsqrt(variance + eps)
+    return h, weight * hf.to(input_dtype)
+
+
+def rotate_half(x: Tensor) -> Tensor:
+    x1 = x[..., : x.shape[-1] // 2]
+    x2 = x[..., x.shape[-1] // 2:]
+    return torch.cat((-x2, x1), dim=-1)
+
+
+def rope_qk(q: Tensor, k: Tensor, cos: Tensor,
+            sin: Tensor) -> tuple[Tensor, Tensor]:
+    """transformers apply_rotary_pos_emb: q, k [B,H,L,D]; cos, sin [B|1,L,D]."""
+    cos = cos.unsqueeze(1)
+    sin = sin.unsqueeze(1)
+    q_embed = (q * cos) + (rotate_half(q) * sin)
+    k_embed = (k * cos) + (rotate_half(k) * sin)
+    return q_embed, k_embed
+
+
+def swiglu(gate: Tensor, up: Tensor) -> Tensor:
+    """Qwen2MLP's act_fn(gate) * up with the silu activation."""
+    return F.silu(gate) * up

@@ -256,6 +256,9 @@ def train(
     # None = the backbone's own loss; "genrec_lce" = chunked linear + CE
     # that never forms the [B*L, V] logits
     loss_implementation: Optional[str] = None,
+    # None = the transformers decoder layer; "genrec_fused" = fused
+    # add+RMSNorm, RoPE and SwiGLU kernels inside every layer
+    layer_implementation: Optional[str] = None,
     # None = expanded, reordered KV cache in generate_topk; "shared_prefix"
     # = one prompt copy + per-beam suffix slots (needs "genrec_gqa")
     beam_cache: Optional[str] = None,
@@ -274,13 +277,15 @@ def train(
 
     model = LCRec(pretrained_path=pretrained_path,
                   attn_implementation=attn_implementation,
-                  loss_implementation=loss_implementation)
+                  loss_implementation=loss_implementation,
+                  layer_implementation=layer_implementation)
     if backbone_config is not None:
         from genrec_amd.models.lcrec import default_qwen_config
 
         model = LCRec(config=default_qwen_config(**backbone_config),
                       attn_implementation=attn_implementation,
-                      loss_implementation=loss_implementation)
+                      loss_implementation=loss_implementation,
+                      layer_implementation=layer_implementation)
     model.add_codebook_tokens(n_codebooks, codebook_size)
     if checkpoint_path and os.path.isdir(checkpoint_path):
         model.load_pretrained(checkpoint_path)

@@ -81,6 +81,9 @@ def train(
     eval_max_batches: Optional[int] = None,
     # None = transformers default; "genrec_gqa" = project GQA flash kernel
     attn_implementation: Optional[str] = None,
+    # None = the transformers decoder layer; "genrec_fused" = fused
+    # add+RMSNorm, RoPE and SwiGLU kernels inside every layer
+    layer_implementation: Optional[str] = None,
 ):
     common.enable_tuned_gemms()
     ctx = init_distributed()
@@ -95,7 +98,8 @@ def train(
         cfg = default_qwen_config(**backbone_config)
     model = Query2Embedding(pretrained_path=pretrained_path, config=cfg,
                             gradient_checkpointing=gradient_checkpointing,
-                            attn_implementation=attn_implementation
+                            attn_implementation=attn_implementation,
+                            layer_implementation=layer_implementation
                             ).to(device)
     broadcast_parameters(model)
     opt = torch.optim.AdamW(model.parameters(), lr=learning_rate,

@@ -32,6 +32,7 @@ sources = [
     "csrc/kernels/attention_gqa.hip",
     "csrc/kernels/attention_beam.hip",
     "csrc/kernels/skinny_gemm.hip",
+    "csrc/kernels/llm_layer.hip",
 ]
 
 cxx_flags = ["-O3", "-std=c++17"]

@@ -186,7 +186,52 @@ def build_cases():
     def csum():
         return ops.ext().colsum(x)
 
+    # Qwen2 layer kernels: 300 rows of d = 1536 (3 chunks per lane, 75
+    # blocks of dw partials, a residual and an incoming dh), RoPE over
+    # 12 + 2 heads read through [B,L,H*D] transpose views, SwiGLU on the
+    # two halves of one [rows, 2*I] buffer
+    e = ops.ext()
+    nx = torch.randn(300, 1536, device=dev, dtype=torch.bfloat16)
+    nres, ndn, ndh = (torch.randn_like(nx) for _ in range(3))
+    nw = torch.randn(1536, device=dev, dtype=torch.bfloat16)
+
+    def addnorm_fwd():
+        return e.add_rms_norm_fwd(nx, nres, nw, 1e-6)
+
+    nh, _, ninv = e.add_rms_norm_fwd(nx, nres, nw, 1e-6)
+
+    def addnorm_bwd():
+        return e.add_rms_norm_bwd(ndn, ndh, nh, nw, ninv)
+
+    rq = torch.randn(2, 70, 12 * Dg, device=dev, dtype=torch.bfloat16) \
+        .view(2, 70, 12, Dg).transpose(1, 2)
+    rk = torch.randn(2, 70, 2 * Dg, device=dev, dtype=torch.bfloat16) \
+        .view(2, 70, 2, Dg).transpose(1, 2)
+    rcos = torch.randn(2, 70, Dg, device=dev, dtype=torch.bfloat16)
+    rsin = torch.randn_like(rcos)
+
+    def rope_fwd():
+        return e.rope_qk_fwd(rq, rk, rcos, rsin, False)
+
+    def rope_bwd():
+        return e.rope_qk_fwd(rq, rk, rcos, rsin, True)
+
+    sgu = torch.randn(37, 2 * 8960, device=dev, dtype=torch.bfloat16)
+    sdy = torch.randn(37, 8960, device=dev, dtype=torch.bfloat16)
+
+    def swiglu_fwd():
+        return e.swiglu_fwd(sgu[:, :8960], sgu[:, 8960:])
+
+    def swiglu_bwd():
+        return e.swiglu_bwd(sdy, sgu[:, :8960], sgu[:, 8960:])
+
     return [
+        ("add_rms_norm_fwd(h,n,inv_rms)", addnorm_fwd, 0.0),
+        ("add_rms_norm_bwd(dx,dw)", addnorm_bwd, 0.0),
+        ("rope_qk_fwd", rope_fwd, 0.0),
+        ("rope_qk_fwd(inverse)", rope_bwd, 0.0),
+        ("swiglu_fwd", swiglu_fwd, 0.0),
+        ("swiglu_bwd(dgate,dup)", swiglu_bwd, 0.0),
         ("attn_fwd_mfma", attn_fwd, 0.0),
         ("attn_bwd_ds(8-wave)", attn_bwd, 0.0),
         ("attn_fwd_flash", flash_fwd, 0.0),
