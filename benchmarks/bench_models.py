@@ -200,6 +200,105 @@ def bench_lcrec(device, steps, warmup, full_size=False, attn_impl="sdpa",
                 ms_per_step=el / steps * 1e3, peak_hbm_gib=peak)
 
 
+class _PackedStep(torch.nn.Module):
+    """Binds the packed batch's host-side max_length, so that the step
+    runner sees a batch of tensors only."""
+
+    def __init__(self, model, max_length):
+        super().__init__()
+        self.model, self.max_length = model, max_length
+
+    def forward(self, **batch):
+        return self.model(max_length=self.max_length, **batch)
+
+
+def bench_lcrec_packing(device, steps, warmup, full_size=False,
+                        loss_impl="hf", vocab=None, layer_impl="hf",
+                        rounds=3, **_):
+    """Padded vs packed LCRec SFT step on the same 32 samples, whose
+    lengths follow an SFT batch's mix (bench_gqa_attention.sft_length_mix)
+    instead of fixed 512-token rows. Both run "genrec_gqa", eagerly (no
+    hipGraph), on identically initialised models; the variants alternate
+    for `rounds` rounds of `steps` steps and the median round is reported.
+    The last 8 tokens of every sample are supervised."""
+    import statistics
+
+    from bench_gqa_attention import sft_length_mix
+    from genrec_amd.models.lcrec import LCRec, default_qwen_config
+
+    lens = sft_length_mix() if full_size else [5, 70, 33, 64]
+    n, lmax, real = len(lens), max(lens), sum(lens)
+    T = -(-real // 64) * 64
+
+    def make():
+        torch.manual_seed(0)
+        cfg = default_qwen_config() if full_size else default_qwen_config(
+            vocab_size=2048, hidden_size=256, num_layers=4, num_heads=4,
+            num_kv_heads=2, intermediate_size=512)
+        if vocab is not None:
+            cfg.vocab_size = vocab
+        m = LCRec(config=cfg, attn_implementation="genrec_gqa",
+                  loss_implementation=None if loss_impl == "hf"
+                  else loss_impl,
+                  layer_implementation=None if layer_impl == "hf"
+                  else layer_impl)
+        m.add_codebook_tokens(5, 256)
+        if vocab is not None:
+            m.model.resize_token_embeddings(vocab + 5 * 256)
+            m.model.config.vocab_size = vocab + 5 * 256
+        if full_size:
+            m.gradient_checkpointing_enable()
+        m = m.to(device)
+        if device.type == "cuda":
+            m = m.to(torch.bfloat16)
+        return m.train()
+
+    m_pad, m_pack = make(), make()
+    V = m_pad.model.config.vocab_size
+    lt = torch.tensor(lens, device=device)
+    valid = torch.arange(lmax, device=device)[None, :] < lt[:, None]
+    ids = torch.randint(0, V, (n, lmax), device=device) * valid
+    pos = torch.arange(lmax, device=device).expand(n, lmax)
+    labels = ids.masked_fill(~(valid & (pos >= (lt[:, None] - 8))
+                               & (pos > 0)), -100)
+    p_ids = ids.new_zeros(1, T)
+    p_lab = ids.new_full((1, T), -100)
+    p_pos = ids.new_zeros(1, T)
+    p_ids[0, :real], p_lab[0, :real], p_pos[0, :real] = \
+        ids[valid], labels[valid], pos[valid]
+    cu = torch.tensor([0] + torch.tensor(lens).cumsum(0).tolist(),
+                      dtype=torch.int32, device=device)
+    run = {
+        "padded": _graph_step(
+            m_pad, {"input_ids": ids, "attention_mask": valid.long(),
+                    "labels": labels},
+            lambda out: out.loss, device, use_graph=False),
+        "packed": _graph_step(
+            _PackedStep(m_pack, lmax),
+            {"input_ids": p_ids, "labels": p_lab, "position_ids": p_pos,
+             "cu_seq_lens": cu},
+            lambda out: out.loss, device, use_graph=False),
+    }
+    for name in run:
+        _timeit(run[name], 0, warmup, device)
+    ms = {name: [] for name in run}
+    for _ in range(rounds):
+        for name in run:
+            ms[name].append(_timeit(run[name], steps, 0, device)
+                            / steps * 1e3)
+    med = {name: statistics.median(v) for name, v in ms.items()}
+    return dict(model="lcrec-qwen2-1.5b" if full_size else "lcrec-tiny",
+                attn="genrec_gqa", loss=loss_impl, layers=layer_impl,
+                vocab=V, step="eager", samples=n, real_tokens=real,
+                padded_tokens=n * lmax, packed_tokens=T, max_len=lmax,
+                padded_ms_per_step=med["padded"],
+                packed_ms_per_step=med["packed"],
+                padded_ms_rounds=ms["padded"], packed_ms_rounds=ms["packed"],
+                packed_speedup=med["padded"] / med["packed"],
+                samples_per_s=n / med["packed"] * 1e3,
+                ms_per_step=med["packed"], rounds=rounds)
+
+
 def bench_cobra(device, steps, warmup):
     """COBRA train step (config/cobra/amazon.gin: B=32, C=3, d_model=384,
     6 heads, 4 layers, T=20 items -> interleaved L=80 on the flash
@@ -250,6 +349,9 @@ def main():
                    help="supervise only the last K positions per sample")
     p.add_argument("--lcrec-eager", action="store_true",
                    help="no hipGraph capture of the LCRec step")
+    p.add_argument("--lcrec-packing", action="store_true",
+                   help="padded vs packed SFT step on one batch of mixed "
+                        "lengths (genrec_gqa, eager step)")
     p.add_argument("--out", default=None)
     args = p.parse_args()
     device = torch.device("cuda:0") if torch.cuda.is_available() \
@@ -266,8 +368,11 @@ def main():
             kw["vocab"] = args.lcrec_vocab
             kw["response_tokens"] = args.lcrec_response_tokens
             kw["eager_step"] = args.lcrec_eager
+        bench = BENCHES[name]
+        if name == "lcrec" and args.lcrec_packing:
+            bench = bench_lcrec_packing
         try:
-            r = BENCHES[name](device, args.steps, args.warmup, **kw)
+            r = bench(device, args.steps, args.warmup, **kw)
         except Exception as e:  # keep other models running
             print(json.dumps({"model": name, "error": str(e)}), flush=True)
             continue

@@ -130,6 +130,13 @@ std::vector<torch::Tensor> gqa_attn_bwd(
     torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
     torch::Tensor out, torch::Tensor lse,
     c10::optional<torch::Tensor> key_pad, double scale, bool causal);
+std::vector<torch::Tensor> gqa_varlen_fwd(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    torch::Tensor cu_seqlens, int64_t max_seqlen, double scale);
+std::vector<torch::Tensor> gqa_varlen_bwd(
+    torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    torch::Tensor out, torch::Tensor lse, torch::Tensor cu_seqlens,
+    int64_t max_seqlen, double scale);
 
 torch::Tensor beam_attn_fwd(torch::Tensor q, torch::Tensor k_pre,
                             torch::Tensor v_pre,
@@ -231,6 +238,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "grouped-query flash attention fwd (D 64/128) -> (out, lse)");
   m.def("gqa_attn_bwd", &genrec::gqa_attn_bwd,
         "grouped-query flash attention bwd (deterministic) -> (dq, dk, dv)");
+  m.def("gqa_varlen_fwd", &genrec::gqa_varlen_fwd,
+        "packed-sequence causal GQA attention fwd: q[T,Hq,D], k/v[T,Hkv,D], "
+        "cu_seqlens int32 [S+1] -> (out[T,Hq,D], lse[Hq,T])");
+  m.def("gqa_varlen_bwd", &genrec::gqa_varlen_bwd,
+        "packed-sequence causal GQA attention bwd (deterministic) -> "
+        "(dq, dk, dv) as [T,H,D]");
   m.def("beam_attn_fwd", &genrec::beam_attn_fwd,
         "shared-prefix beam-search decode attention (D 64/128) -> out",
         py::arg("q"), py::arg("k_pre"), py::arg("v_pre"), py::arg("pre_pad"),

@@ -26,6 +26,20 @@
 // KV caches go through without a copy). out is [B,Lq,Hq,D] contiguous;
 // dq/dk/dv are allocated [B,L,H,D] contiguous and returned as [B,H,L,D]
 // transpose views, which is the layout the projection GEMMs' grads want.
+//
+// Variable-length mode (VARLEN = true; gqa_varlen_fwd / gqa_varlen_bwd):
+// q/k/v are token-major [T,H,D] views of S packed sequences and cu_seqlens
+// [S+1] (int32, device) gives sequence s the tokens [cu[s], cu[s+1]). A
+// sequence takes the place of a batch item: blockIdx.x walks (s, head), the
+// base pointers move to token cu[s], Lq = Lk = cu[s+1] - cu[s], causal. The
+// tile decomposition, loop order and arithmetic of a sequence are those of
+// the fixed-length kernel on that sequence alone with B = 1, so the results
+// are bit-identical. The grid is sized by the host's max_seqlen; a block
+// whose tile starts at or beyond its sequence's length leaves before its
+// first barrier. Offsets are clamped to [0,T] and to end >= start, so no
+// cu_seqlens content addresses outside the tensors. out is [T,Hq,D], lse
+// and delta are [Hq,T], dq/dk/dv are [T,H,D]; all are zero-filled by the
+// host, which is what tokens beyond cu[S] and empty sequences keep.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -36,24 +50,51 @@ namespace genrec {
 
 namespace {
 
+// Token range of packed sequence s, clamped so that it lies inside [0,T].
+__device__ __forceinline__ void gqa_seq_range(const int* __restrict__ cu,
+                                              int s, int T, int* start,
+                                              int* len) {
+  const int a = min(max(cu[s], 0), T);
+  const int e = min(max(cu[s + 1], a), T);
+  *start = a;
+  *len = e - a;
+}
+
 // ------------------------------------------------------------------ forward
 
-template <int D>
+template <int D, bool VARLEN>
 __global__ void __launch_bounds__(256)
 gqa_fwd_kernel(const __hip_bfloat16* __restrict__ q,
                const __hip_bfloat16* __restrict__ k,
                const __hip_bfloat16* __restrict__ v,
                const bool* __restrict__ key_pad,  // null | [B,Lk]
-               __hip_bfloat16* __restrict__ out,  // [B,Lq,Hq,D]
-               float* __restrict__ lse,           // [B,Hq,Lq]
+               __hip_bfloat16* __restrict__ out,  // [B,Lq,Hq,D] | [T,Hq,D]
+               float* __restrict__ lse,           // [B,Hq,Lq] | [Hq,T]
                int Hq, int Hkv, int Lq, int Lk, float scale, bool causal,
                int64_t q_sb, int64_t q_sh, int64_t q_sl,
                int64_t k_sb, int64_t k_sh, int64_t k_sl,
-               int64_t v_sb, int64_t v_sh, int64_t v_sl) {
+               int64_t v_sb, int64_t v_sh, int64_t v_sl,
+               const int* __restrict__ cu, int T) {  // VARLEN only
   constexpr int RS = D * 2;
   const int b = blockIdx.x / Hq, h = blockIdx.x % Hq;
   const int hk = h / (Hq / Hkv);
   const int q0 = blockIdx.y * TILE;
+  int64_t tok0, rowb;  // first out row of b; first lse entry of (b, h)
+  if constexpr (VARLEN) {
+    int start;
+    gqa_seq_range(cu, b, T, &start, &Lq);
+    Lk = Lq;
+    if (q0 >= Lq) return;  // uniform per block, before any barrier
+    q_sb = k_sb = v_sb = 0;  // the sequence's base is its first token
+    q += (int64_t)start * q_sl;
+    k += (int64_t)start * k_sl;
+    v += (int64_t)start * v_sl;
+    tok0 = start;
+    rowb = (int64_t)h * T + start;
+  } else {
+    tok0 = (int64_t)b * Lq;
+    rowb = ((int64_t)b * Hq + h) * Lq;
+  }
   const int off = Lk - Lq;  // query row i sits at absolute position i + off
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -171,13 +212,13 @@ gqa_fwd_kernel(const __hip_bfloat16* __restrict__ q,
     int i = q0 + strip + row_grp + r;
     if (i >= Lq) continue;
     float inv = (l_row[r] > 0.f) ? 1.0f / l_row[r] : 0.f;
-    int64_t ob = (((int64_t)b * Lq + i) * Hq + h) * D;
+    int64_t ob = ((tok0 + i) * Hq + h) * D;
 #pragma unroll
     for (int f = 0; f < D / 16; ++f) {
       out[ob + f * 16 + col_base] = __float2bfloat16(accO[f][r] * inv);
     }
     if (col_base == 0) {
-      lse[((int64_t)b * Hq + h) * Lq + i] =
+      lse[rowb + i] =
           (l_row[r] > 0.f) ? m_row[r] + __logf(l_row[r]) : 0.f;
     }
   }
@@ -234,7 +275,7 @@ gqa_delta_kernel(const __hip_bfloat16* __restrict__ dout,  // [B,Lq,Hq,D] view
 
 // ------------------------------------------------------- backward: dK, dV
 
-template <int D>
+template <int D, bool VARLEN>
 __global__ void __launch_bounds__(256)
 gqa_bwd_dkdv_kernel(const __hip_bfloat16* __restrict__ dout,
                     const __hip_bfloat16* __restrict__ q,
@@ -249,11 +290,25 @@ gqa_bwd_dkdv_kernel(const __hip_bfloat16* __restrict__ dout,
                     int64_t do_sb, int64_t do_sh, int64_t do_sl,
                     int64_t q_sb, int64_t q_sh, int64_t q_sl,
                     int64_t k_sb, int64_t k_sh, int64_t k_sl,
-                    int64_t v_sb, int64_t v_sh, int64_t v_sl) {
+                    int64_t v_sb, int64_t v_sh, int64_t v_sl,
+                    const int* __restrict__ cu, int T) {  // VARLEN only
   constexpr int RS = D * 2;
   const int b = blockIdx.x / Hkv, hk = blockIdx.x % Hkv;
   const int grp = Hq / Hkv;
   const int kt0 = blockIdx.y * TILE;
+  int64_t tok0 = (int64_t)b * Lk;  // first dk/dv row of b
+  int start = 0;
+  if constexpr (VARLEN) {
+    gqa_seq_range(cu, b, T, &start, &Lq);
+    Lk = Lq;
+    if (kt0 >= Lk) return;  // uniform per block, before any barrier
+    do_sb = q_sb = k_sb = v_sb = 0;
+    dout += (int64_t)start * do_sl;
+    q += (int64_t)start * q_sl;
+    k += (int64_t)start * k_sl;
+    v += (int64_t)start * v_sl;
+    tok0 = start;
+  }
   const int off = Lk - Lq;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -303,7 +358,8 @@ gqa_bwd_dkdv_kernel(const __hip_bfloat16* __restrict__ dout,
     const int h = hk * grp + hh;
     const __hip_bfloat16* qb = q + (int64_t)b * q_sb + (int64_t)h * q_sh;
     const __hip_bfloat16* dob = dout + (int64_t)b * do_sb + (int64_t)h * do_sh;
-    const int64_t rowb = ((int64_t)b * Hq + h) * Lq;
+    const int64_t rowb =
+        VARLEN ? (int64_t)h * T + start : ((int64_t)b * Hq + h) * Lq;
     for (int q0 = q_begin; q0 < Lq; q0 += TILE) {
       __syncthreads();  // previous tile's qs/dos/qt/dot/dst/pt consumed
       gstage<D, true, true>(qb, q_sl, q0, Lq, qs, qt, tid);
@@ -368,7 +424,7 @@ gqa_bwd_dkdv_kernel(const __hip_bfloat16* __restrict__ dout,
   for (int r = 0; r < 4; ++r) {
     int j = kt0 + strip + row_grp + r;
     if (j >= Lk) continue;
-    int64_t ob = (((int64_t)b * Lk + j) * Hkv + hk) * D;
+    int64_t ob = ((tok0 + j) * Hkv + hk) * D;
 #pragma unroll
     for (int f = 0; f < D / 16; ++f) {
       dk[ob + f * 16 + col_base] = __float2bfloat16(acck[f][r]);
@@ -379,7 +435,7 @@ gqa_bwd_dkdv_kernel(const __hip_bfloat16* __restrict__ dout,
 
 // ----------------------------------------------------------- backward: dQ
 
-template <int D>
+template <int D, bool VARLEN>
 __global__ void __launch_bounds__(256)
 gqa_bwd_dq_kernel(const __hip_bfloat16* __restrict__ dout,
                   const __hip_bfloat16* __restrict__ q,
@@ -393,11 +449,29 @@ gqa_bwd_dq_kernel(const __hip_bfloat16* __restrict__ dout,
                   int64_t do_sb, int64_t do_sh, int64_t do_sl,
                   int64_t q_sb, int64_t q_sh, int64_t q_sl,
                   int64_t k_sb, int64_t k_sh, int64_t k_sl,
-                  int64_t v_sb, int64_t v_sh, int64_t v_sl) {
+                  int64_t v_sb, int64_t v_sh, int64_t v_sl,
+                  const int* __restrict__ cu, int T) {  // VARLEN only
   constexpr int RS = D * 2;
   const int b = blockIdx.x / Hq, h = blockIdx.x % Hq;
   const int hk = h / (Hq / Hkv);
   const int q0 = blockIdx.y * TILE;
+  int64_t tok0, rowb;  // first dq row of b; first lse/delta entry of (b, h)
+  if constexpr (VARLEN) {
+    int start;
+    gqa_seq_range(cu, b, T, &start, &Lq);
+    Lk = Lq;
+    if (q0 >= Lq) return;  // uniform per block, before any barrier
+    do_sb = q_sb = k_sb = v_sb = 0;
+    dout += (int64_t)start * do_sl;
+    q += (int64_t)start * q_sl;
+    k += (int64_t)start * k_sl;
+    v += (int64_t)start * v_sl;
+    tok0 = start;
+    rowb = (int64_t)h * T + start;
+  } else {
+    tok0 = (int64_t)b * Lq;
+    rowb = ((int64_t)b * Hq + h) * Lq;
+  }
   const int off = Lk - Lq;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -420,7 +494,6 @@ gqa_bwd_dq_kernel(const __hip_bfloat16* __restrict__ dout,
   gstage<D, true, false>(dout + (int64_t)b * do_sb + (int64_t)h * do_sh,
                          do_sl, q0, Lq, dos, nullptr, tid);
 
-  const int64_t rowb = ((int64_t)b * Hq + h) * Lq;
   float lse_r[4], dl_r[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -497,7 +570,7 @@ gqa_bwd_dq_kernel(const __hip_bfloat16* __restrict__ dout,
   for (int r = 0; r < 4; ++r) {
     int i = q0 + strip + row_grp + r;
     if (i >= Lq) continue;
-    int64_t ob = (((int64_t)b * Lq + i) * Hq + h) * D;
+    int64_t ob = ((tok0 + i) * Hq + h) * D;
 #pragma unroll
     for (int f = 0; f < D / 16; ++f) {
       dq[ob + f * 16 + col_base] = __float2bfloat16(accq[f][r]);
@@ -568,87 +641,150 @@ void gqa_allow_lds(K kernel, size_t smem, bool* done) {
 
 constexpr int kMaxDev = 64;
 
-template <int D>
+// batch / head / row strides of one operand as the kernels take them
+struct GqaStrides {
+  int64_t b, h, l;
+};
+// [B,H,L,D] view
+GqaStrides gqa_bhld(const torch::Tensor& t) {
+  return {t.stride(0), t.stride(1), t.stride(2)};
+}
+// [B,L,H,D] view (dout)
+GqaStrides gqa_blhd(const torch::Tensor& t) {
+  return {t.stride(0), t.stride(2), t.stride(1)};
+}
+// token-major [T,H,D] view of packed sequences: no batch stride
+GqaStrides gqa_thd(const torch::Tensor& t) {
+  return {0, t.stride(1), t.stride(0)};
+}
+
+const __hip_bfloat16* gqa_cptr(const torch::Tensor& t) {
+  return reinterpret_cast<const __hip_bfloat16*>(t.data_ptr());
+}
+__hip_bfloat16* gqa_ptr(torch::Tensor& t) {
+  return reinterpret_cast<__hip_bfloat16*>(t.data_ptr());
+}
+
+// s.B counts sequences and s.Lq = s.Lk = max_seqlen when VARLEN; cu/T are
+// then the device offsets and the token count, else null/0.
+template <int D, bool VARLEN>
 void gqa_launch_fwd(const GqaShape& s, const torch::Tensor& q,
                     const torch::Tensor& k, const torch::Tensor& v,
                     const bool* kp, torch::Tensor& out, torch::Tensor& lse,
-                    float scale, bool causal) {
+                    float scale, bool causal, const int* cu = nullptr,
+                    int T = 0) {
   dim3 grid(s.B * s.Hq, (s.Lq + TILE - 1) / TILE);
   size_t smem = 2 * TILE * D * 2 + D * 128 + TILE * 128;
   static bool done[kMaxDev] = {};
-  gqa_allow_lds(gqa_fwd_kernel<D>, smem, &done[q.get_device() % kMaxDev]);
+  gqa_allow_lds(gqa_fwd_kernel<D, VARLEN>, smem,
+                &done[q.get_device() % kMaxDev]);
+  const GqaStrides qs = VARLEN ? gqa_thd(q) : gqa_bhld(q),
+                   ks = VARLEN ? gqa_thd(k) : gqa_bhld(k),
+                   vs = VARLEN ? gqa_thd(v) : gqa_bhld(v);
   auto stream = at::cuda::getCurrentHIPStream();
-  hipLaunchKernelGGL(gqa_fwd_kernel<D>, grid, dim3(256), smem, stream,
-      reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
-      reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
-      reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()), kp,
-      reinterpret_cast<__hip_bfloat16*>(out.data_ptr()),
+  hipLaunchKernelGGL((gqa_fwd_kernel<D, VARLEN>), grid, dim3(256), smem,
+      stream, gqa_cptr(q), gqa_cptr(k), gqa_cptr(v), kp, gqa_ptr(out),
       lse.data_ptr<float>(), s.Hq, s.Hkv, s.Lq, s.Lk, scale, causal,
-      q.stride(0), q.stride(1), q.stride(2),
-      k.stride(0), k.stride(1), k.stride(2),
-      v.stride(0), v.stride(1), v.stride(2));
+      qs.b, qs.h, qs.l, ks.b, ks.h, ks.l, vs.b, vs.h, vs.l, cu, T);
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
-template <int D>
+template <int D, bool VARLEN>
 void gqa_launch_bwd(const GqaShape& s, const torch::Tensor& dout,
                     const torch::Tensor& q, const torch::Tensor& k,
                     const torch::Tensor& v, const torch::Tensor& out,
                     const torch::Tensor& lse, const bool* kp,
                     torch::Tensor& delta, torch::Tensor& dq,
                     torch::Tensor& dk, torch::Tensor& dv, float scale,
-                    bool causal) {
+                    bool causal, const int* cu = nullptr, int T = 0) {
   auto stream = at::cuda::getCurrentHIPStream();
   const int dev = q.get_device() % kMaxDev;
-  const __hip_bfloat16* dop =
-      reinterpret_cast<const __hip_bfloat16*>(dout.data_ptr());
-  const __hip_bfloat16* qp =
-      reinterpret_cast<const __hip_bfloat16*>(q.data_ptr());
-  const __hip_bfloat16* kp16 =
-      reinterpret_cast<const __hip_bfloat16*>(k.data_ptr());
-  const __hip_bfloat16* vp =
-      reinterpret_cast<const __hip_bfloat16*>(v.data_ptr());
-  // dout is a [B,Lq,Hq,D] view: batch, head, row strides
-  const int64_t do_sb = dout.stride(0), do_sh = dout.stride(2),
-                do_sl = dout.stride(1);
+  const __hip_bfloat16* dop = gqa_cptr(dout);
+  const __hip_bfloat16* qp = gqa_cptr(q);
+  const __hip_bfloat16* kp16 = gqa_cptr(k);
+  const __hip_bfloat16* vp = gqa_cptr(v);
+  const GqaStrides ds = VARLEN ? gqa_thd(dout) : gqa_blhd(dout),
+                   qs = VARLEN ? gqa_thd(q) : gqa_bhld(q),
+                   ks = VARLEN ? gqa_thd(k) : gqa_bhld(k),
+                   vs = VARLEN ? gqa_thd(v) : gqa_bhld(v);
   {
+    // packed sequences: the [T,Hq,D] rows are one batch item of T rows
+    // (delta is per row, so sequence boundaries do not matter to it)
     constexpr int rows_per_block = 256 / (D / 8);
-    int64_t n_rows = (int64_t)s.B * s.Hq * s.Lq;
+    const int dl_L = VARLEN ? T : s.Lq;
+    int64_t n_rows = (int64_t)(VARLEN ? 1 : s.B) * s.Hq * dl_L;
     dim3 grid((unsigned int)((n_rows + rows_per_block - 1) / rows_per_block));
     hipLaunchKernelGGL(gqa_delta_kernel<D>, grid, dim3(256), 0, stream, dop,
-        reinterpret_cast<const __hip_bfloat16*>(out.data_ptr()),
-        delta.data_ptr<float>(), s.Hq, s.Lq, n_rows, do_sb, do_sh, do_sl);
+        gqa_cptr(out), delta.data_ptr<float>(), s.Hq, dl_L, n_rows, ds.b,
+        ds.h, ds.l);
     C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   {
     dim3 grid(s.B * s.Hkv, (s.Lk + TILE - 1) / TILE);
     size_t smem = 4 * TILE * D * 2 + 2 * D * 128 + 2 * TILE * 128;
     static bool done[kMaxDev] = {};
-    gqa_allow_lds(gqa_bwd_dkdv_kernel<D>, smem, &done[dev]);
-    hipLaunchKernelGGL(gqa_bwd_dkdv_kernel<D>, grid, dim3(256), smem, stream,
-        dop, qp, kp16, vp, lse.data_ptr<float>(), delta.data_ptr<float>(),
-        kp, reinterpret_cast<__hip_bfloat16*>(dk.data_ptr()),
-        reinterpret_cast<__hip_bfloat16*>(dv.data_ptr()),
-        s.Hq, s.Hkv, s.Lq, s.Lk, scale, causal, do_sb, do_sh, do_sl,
-        q.stride(0), q.stride(1), q.stride(2),
-        k.stride(0), k.stride(1), k.stride(2),
-        v.stride(0), v.stride(1), v.stride(2));
+    gqa_allow_lds(gqa_bwd_dkdv_kernel<D, VARLEN>, smem, &done[dev]);
+    hipLaunchKernelGGL((gqa_bwd_dkdv_kernel<D, VARLEN>), grid, dim3(256),
+        smem, stream, dop, qp, kp16, vp, lse.data_ptr<float>(),
+        delta.data_ptr<float>(), kp, gqa_ptr(dk), gqa_ptr(dv),
+        s.Hq, s.Hkv, s.Lq, s.Lk, scale, causal, ds.b, ds.h, ds.l,
+        qs.b, qs.h, qs.l, ks.b, ks.h, ks.l, vs.b, vs.h, vs.l, cu, T);
     C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   {
     dim3 grid(s.B * s.Hq, (s.Lq + TILE - 1) / TILE);
     size_t smem = 4 * TILE * D * 2 + D * 128 + TILE * 128;
     static bool done[kMaxDev] = {};
-    gqa_allow_lds(gqa_bwd_dq_kernel<D>, smem, &done[dev]);
-    hipLaunchKernelGGL(gqa_bwd_dq_kernel<D>, grid, dim3(256), smem, stream,
-        dop, qp, kp16, vp, lse.data_ptr<float>(), delta.data_ptr<float>(),
-        kp, reinterpret_cast<__hip_bfloat16*>(dq.data_ptr()),
-        s.Hq, s.Hkv, s.Lq, s.Lk, scale, causal, do_sb, do_sh, do_sl,
-        q.stride(0), q.stride(1), q.stride(2),
-        k.stride(0), k.stride(1), k.stride(2),
-        v.stride(0), v.stride(1), v.stride(2));
+    gqa_allow_lds(gqa_bwd_dq_kernel<D, VARLEN>, smem, &done[dev]);
+    hipLaunchKernelGGL((gqa_bwd_dq_kernel<D, VARLEN>), grid, dim3(256), smem,
+        stream, dop, qp, kp16, vp, lse.data_ptr<float>(),
+        delta.data_ptr<float>(), kp, gqa_ptr(dq),
+        s.Hq, s.Hkv, s.Lq, s.Lk, scale, causal, ds.b, ds.h, ds.l,
+        qs.b, qs.h, qs.l, ks.b, ks.h, ks.l, vs.b, vs.h, vs.l, cu, T);
     C10_HIP_KERNEL_LAUNCH_CHECK();
   }
+}
+
+// ---- packed sequences
+
+bool gqa_ok_strides_thd(const torch::Tensor& t) {
+  return t.stride(2) == 1 && t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0 &&
+         reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+
+// s.B = number of sequences, s.Lq = s.Lk = max_seqlen; returns T
+int gqa_varlen_check(const torch::Tensor& q, const torch::Tensor& k,
+                     const torch::Tensor& v, const torch::Tensor& cu,
+                     int64_t max_seqlen, GqaShape* s) {
+  TORCH_CHECK(q.is_cuda() && k.is_cuda() && v.is_cuda() && cu.is_cuda(),
+              "gqa_varlen: q/k/v/cu_seqlens must be GPU tensors");
+  TORCH_CHECK(q.scalar_type() == torch::kBFloat16 &&
+                  k.scalar_type() == torch::kBFloat16 &&
+                  v.scalar_type() == torch::kBFloat16,
+              "gqa_varlen: q/k/v must be bfloat16");
+  TORCH_CHECK(q.dim() == 3 && k.dim() == 3 && v.dim() == 3,
+              "gqa_varlen: q/k/v must be [T,H,D]");
+  TORCH_CHECK(cu.scalar_type() == torch::kInt32 && cu.dim() == 1 &&
+                  cu.size(0) >= 1 && cu.is_contiguous(),
+              "gqa_varlen: cu_seqlens must be a contiguous int32 [S+1] "
+              "tensor");
+  const int64_t T = q.size(0);
+  s->B = (int)(cu.size(0) - 1);
+  s->Hq = q.size(1); s->D = q.size(2); s->Hkv = k.size(1);
+  TORCH_CHECK(s->D == 64 || s->D == 128,
+              "gqa_varlen: head dim must be 64 or 128, got ", s->D);
+  TORCH_CHECK(k.size(0) == T && k.size(2) == s->D && v.sizes() == k.sizes(),
+              "gqa_varlen: k/v must be [T,Hkv,D] matching q");
+  TORCH_CHECK(s->Hkv >= 1 && s->Hq % s->Hkv == 0,
+              "gqa_varlen: Hq (", s->Hq, ") must be a multiple of Hkv (",
+              s->Hkv, ")");
+  TORCH_CHECK(T < (int64_t)1 << 31, "gqa_varlen: too many tokens");
+  TORCH_CHECK(max_seqlen >= 0 && (max_seqlen + TILE - 1) / TILE <= 65535,
+              "gqa_varlen: max_seqlen out of range");
+  TORCH_CHECK((int64_t)s->B * s->Hq < (int64_t)1 << 31,
+              "gqa_varlen: too many sequences");
+  s->Lq = s->Lk = (int)max_seqlen;
+  return (int)T;
 }
 
 }  // namespace
@@ -670,9 +806,9 @@ std::vector<torch::Tensor> gqa_attn_fwd(
   auto lse = torch::empty({s.B, s.Hq, s.Lq},
                           q.options().dtype(torch::kFloat32));
   if (s.D == 64) {
-    gqa_launch_fwd<64>(s, qn, kn, vn, kp, out, lse, (float)scale, causal);
+    gqa_launch_fwd<64, false>(s, qn, kn, vn, kp, out, lse, (float)scale, causal);
   } else {
-    gqa_launch_fwd<128>(s, qn, kn, vn, kp, out, lse, (float)scale, causal);
+    gqa_launch_fwd<128, false>(s, qn, kn, vn, kp, out, lse, (float)scale, causal);
   }
   return {out, lse};
 }
@@ -711,13 +847,72 @@ std::vector<torch::Tensor> gqa_attn_bwd(
   auto dk = torch::empty({s.B, s.Lk, s.Hkv, s.D}, k.options());
   auto dv = torch::empty({s.B, s.Lk, s.Hkv, s.D}, v.options());
   if (s.D == 64) {
-    gqa_launch_bwd<64>(s, don, qn, kn, vn, out, lse, kp, delta, dq, dk, dv,
+    gqa_launch_bwd<64, false>(s, don, qn, kn, vn, out, lse, kp, delta, dq, dk, dv,
                        (float)scale, causal);
   } else {
-    gqa_launch_bwd<128>(s, don, qn, kn, vn, out, lse, kp, delta, dq, dk, dv,
+    gqa_launch_bwd<128, false>(s, don, qn, kn, vn, out, lse, kp, delta, dq, dk, dv,
                         (float)scale, causal);
   }
   return {dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2)};
+}
+
+std::vector<torch::Tensor> gqa_varlen_fwd(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    torch::Tensor cu_seqlens, int64_t max_seqlen, double scale) {
+  GqaShape s;
+  const int T = gqa_varlen_check(q, k, v, cu_seqlens, max_seqlen, &s);
+  torch::Tensor qn = gqa_ok_strides_thd(q) ? q : q.contiguous();
+  torch::Tensor kn = gqa_ok_strides_thd(k) ? k : k.contiguous();
+  torch::Tensor vn = gqa_ok_strides_thd(v) ? v : v.contiguous();
+  // zeros: tokens of no sequence (beyond cu[S]) are never written
+  auto out = torch::zeros({T, s.Hq, s.D}, q.options());
+  auto lse = torch::zeros({s.Hq, T}, q.options().dtype(torch::kFloat32));
+  if (T == 0 || s.B == 0 || max_seqlen == 0) return {out, lse};
+  const int* cu = cu_seqlens.data_ptr<int>();
+  if (s.D == 64) {
+    gqa_launch_fwd<64, true>(s, qn, kn, vn, nullptr, out, lse, (float)scale,
+                             true, cu, T);
+  } else {
+    gqa_launch_fwd<128, true>(s, qn, kn, vn, nullptr, out, lse, (float)scale,
+                              true, cu, T);
+  }
+  return {out, lse};
+}
+
+std::vector<torch::Tensor> gqa_varlen_bwd(
+    torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    torch::Tensor out, torch::Tensor lse, torch::Tensor cu_seqlens,
+    int64_t max_seqlen, double scale) {
+  GqaShape s;
+  const int T = gqa_varlen_check(q, k, v, cu_seqlens, max_seqlen, &s);
+  TORCH_CHECK(dout.is_cuda() && dout.scalar_type() == torch::kBFloat16 &&
+                  dout.dim() == 3 && dout.size(0) == T &&
+                  dout.size(1) == s.Hq && dout.size(2) == s.D,
+              "gqa_varlen_bwd: dout must be bf16 [T,Hq,D]");
+  TORCH_CHECK(out.scalar_type() == torch::kBFloat16 &&
+                  out.sizes() == dout.sizes() && out.is_contiguous(),
+              "gqa_varlen_bwd: out must be the contiguous forward output");
+  TORCH_CHECK(lse.scalar_type() == torch::kFloat32 && lse.is_contiguous() &&
+                  lse.dim() == 2 && lse.size(0) == s.Hq && lse.size(1) == T,
+              "gqa_varlen_bwd: lse must be the fp32 [Hq,T] forward lse");
+  torch::Tensor don = gqa_ok_strides_thd(dout) ? dout : dout.contiguous();
+  torch::Tensor qn = gqa_ok_strides_thd(q) ? q : q.contiguous();
+  torch::Tensor kn = gqa_ok_strides_thd(k) ? k : k.contiguous();
+  torch::Tensor vn = gqa_ok_strides_thd(v) ? v : v.contiguous();
+  auto dq = torch::zeros({T, s.Hq, s.D}, q.options());
+  auto dk = torch::zeros({T, s.Hkv, s.D}, k.options());
+  auto dv = torch::zeros({T, s.Hkv, s.D}, v.options());
+  if (T == 0 || s.B == 0 || max_seqlen == 0) return {dq, dk, dv};
+  auto delta = torch::empty({s.Hq, T}, lse.options());
+  const int* cu = cu_seqlens.data_ptr<int>();
+  if (s.D == 64) {
+    gqa_launch_bwd<64, true>(s, don, qn, kn, vn, out, lse, nullptr, delta, dq,
+                             dk, dv, (float)scale, true, cu, T);
+  } else {
+    gqa_launch_bwd<128, true>(s, don, qn, kn, vn, out, lse, nullptr, delta,
+                              dq, dk, dv, (float)scale, true, cu, T);
+  }
+  return {dq, dk, dv};
 }
 
 }  // namespace genrec

@@ -180,23 +180,55 @@ class LCRec(nn.Module):
                 type(self.model).__name__)
         return None
 
-    def forward(self, input_ids, attention_mask=None, labels=None, **kw):
+    def _packed_kwargs(self, input_ids, position_ids, cu_seq_lens,
+                       max_length) -> Dict:
+        """Backbone kwargs of a packed [1,T] row: attention is confined to
+        each sequence by the genrec_gqa adapter through transformers' own
+        cu_seq_lens_* / max_length_* names; no [1,1,T,T] mask is built."""
+        if self.attn_implementation != "genrec_gqa":
+            raise ValueError(
+                'cu_seq_lens (packed sequences) requires '
+                'attn_implementation="genrec_gqa", got '
+                f"{self.attn_implementation!r}")
+        if input_ids.dim() != 2 or input_ids.size(0) != 1:
+            raise ValueError("cu_seq_lens (packed sequences) needs input_ids "
+                             f"[1,T], got {tuple(input_ids.shape)}")
+        if position_ids is None:
+            raise ValueError("cu_seq_lens (packed sequences) needs "
+                             "position_ids that restart at every sequence")
+        cu = cu_seq_lens.to(device=input_ids.device, dtype=torch.int32)
+        max_length = int(max_length) if max_length else input_ids.size(1)
+        return dict(attention_mask={"full_attention": None},
+                    position_ids=position_ids, use_cache=False,
+                    cu_seq_lens_q=cu, cu_seq_lens_k=cu,
+                    max_length_q=max_length, max_length_k=max_length)
+
+    def forward(self, input_ids, attention_mask=None, labels=None,
+                position_ids=None, cu_seq_lens=None, max_length=None, **kw):
+        """cu_seq_lens (int32 [S+1]) marks input_ids [1,T] as S packed
+        sequences with position_ids restarting at each and max_length >=
+        the longest; attention_mask is then unused. It needs
+        attn_implementation="genrec_gqa"."""
+        if cu_seq_lens is not None:
+            extra = self._packed_kwargs(input_ids, position_ids, cu_seq_lens,
+                                        max_length)
+        else:
+            extra = {"attention_mask": attention_mask}
+            if position_ids is not None:
+                extra["position_ids"] = position_ids
         if labels is not None and self.loss_implementation == "genrec_lce":
             parts = self._lce_parts()
             if parts is not None:
-                return self._forward_lce(parts, input_ids, attention_mask,
-                                         labels)
-        return self.model(input_ids=input_ids, attention_mask=attention_mask,
-                          labels=labels)
+                return self._forward_lce(parts, input_ids, labels, extra)
+        return self.model(input_ids=input_ids, labels=labels, **extra)
 
-    def _forward_lce(self, parts, input_ids, attention_mask, labels):
+    def _forward_lce(self, parts, input_ids, labels, extra):
         from transformers.modeling_outputs import CausalLMOutputWithPast
 
         from genrec_amd import ops
 
         backbone, head = parts
-        hidden = backbone(input_ids=input_ids,
-                          attention_mask=attention_mask).last_hidden_state
+        hidden = backbone(input_ids=input_ids, **extra).last_hidden_state
         # the causal-LM shift: position i is scored against token i+1
         shifted = F.pad(labels, (0, 1), value=-100)[..., 1:]
         loss = ops.linear_cross_entropy(

@@ -22,6 +22,12 @@ Beam-search decode can hand the adapter a `SharedPrefixBeamCache` as the
 extra forward keyword `genrec_beam_state`: the step's attention then runs
 `ops.beam_decode_attention` on the cache's one-copy-per-prompt prefix and
 its per-beam suffix slots (LCRec.generate_topk, beam_cache="shared_prefix").
+
+Packed ("padding-free") training hands it transformers' own keywords
+`cu_seq_lens_q`, `cu_seq_lens_k`, `max_length_q`, `max_length_k` with one
+row of T tokens: attention then runs `ops.gqa_varlen_attention`, confined to
+each sequence. On that path nothing falls back to `sdpa`, which would attend
+across sequences; a configuration it cannot honour raises `ValueError`.
 """
 
 from __future__ import annotations
@@ -32,7 +38,7 @@ import torch
 
 from genrec_amd.ops.attention import (
     BEAM_MAX_SUFFIX, beam_decode_attention, gqa_flash_attention,
-    gqa_kernel_supported,
+    gqa_kernel_supported, gqa_varlen_attention,
 )
 
 NAME = "genrec_gqa"
@@ -157,6 +163,50 @@ def genrec_gqa_attention_forward(
     is_causal = kwargs.get("is_causal")
     if is_causal is None:
         is_causal = getattr(module, "is_causal", True)
+
+    cu_q = kwargs.get("cu_seq_lens_q")
+    if cu_q is not None:
+        # packed sequences: one row of T tokens, attention confined to each
+        # sequence by the offsets. sdpa would attend across sequences, so
+        # whatever this path cannot honour raises.
+        cu_k = kwargs.get("cu_seq_lens_k")
+        if cu_k is None:
+            cu_k = cu_q
+        why = None
+        if query.size(0) != 1 or lq != lk:
+            why = "a batch of one row without a cache"
+        elif cu_k is not cu_q and (cu_k.shape != cu_q.shape
+                                   or cu_k.data_ptr() != cu_q.data_ptr()):
+            why = "cu_seq_lens_q and cu_seq_lens_k to be the same offsets"
+        elif kwargs.get("sliding_window") is not None:
+            why = "full attention (no sliding window)"
+        elif dropout > 0.0 and module.training:
+            why = "no attention dropout"
+        elif not is_causal:
+            why = "causal attention"
+        elif kwargs.get("position_bias") is not None:
+            why = "no position_bias"
+        elif kwargs.get("output_attentions", False):
+            why = "output_attentions=False"
+        elif query.size(1) % key.size(1) != 0:
+            why = "Hq to be a multiple of Hkv"
+        if why is not None:
+            raise ValueError(f"{NAME}: packed sequences (cu_seq_lens_q) "
+                             f"need {why}")
+        max_q = kwargs.get("max_length_q")
+        max_k = kwargs.get("max_length_k")
+        max_len = max(int(max_q or 0), int(max_k or 0)) or lq
+        scale = scaling if scaling is not None else query.size(-1) ** -0.5
+        if query.is_cuda and torch.is_autocast_enabled("cuda"):
+            # what autocast does to sdpa's inputs (RoPE leaves them fp32
+            # under fp32 master weights): the kernel takes bf16
+            dt = torch.get_autocast_dtype("cuda")
+            query, key, value = query.to(dt), key.to(dt), value.to(dt)
+        out = gqa_varlen_attention(
+            query[0].transpose(0, 1), key[0].transpose(0, 1),
+            value[0].transpose(0, 1), cu_q, max_len, scale=scale)
+        return out.unsqueeze(0), None         # [1, T, Hq, D]
+
     if (kwargs.get("sliding_window") is not None
             or (dropout > 0.0 and module.training)
             or kwargs.get("output_attentions", False)

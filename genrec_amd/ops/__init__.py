@@ -87,6 +87,8 @@ from genrec_amd.ops.attention import (  # noqa: E402
     hstu_pointwise_attention,
     hstu_fused_attention,
     gqa_flash_attention,
+    gqa_varlen_attention,
+    gqa_varlen_supported,
     beam_decode_attention,
     beam_decode_supported,
 )
@@ -121,6 +123,8 @@ __all__ = [
     "hstu_pointwise_attention",
     "hstu_fused_attention",
     "gqa_flash_attention",
+    "gqa_varlen_attention",
+    "gqa_varlen_supported",
     "beam_decode_attention",
     "beam_decode_supported",
     "project_cross_kv",

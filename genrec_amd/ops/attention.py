@@ -574,6 +574,81 @@ def gqa_flash_attention(
                                scale=scale, causal=causal)
 
 
+class _GqaVarlenAttnFn(torch.autograd.Function):
+    """Packed-sequence causal GQA attention (the VARLEN instantiations of
+    csrc/kernels/attention_gqa.hip). cu_seqlens stays on the device and
+    max_seqlen only sizes the grid: no host sync, forward or backward."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, cu_seqlens, max_seqlen, scale):
+        from genrec_amd import ops
+
+        out, lse = ops.ext().gqa_varlen_fwd(q, k, v, cu_seqlens, max_seqlen,
+                                            scale)
+        ctx.save_for_backward(q, k, v, out, lse, cu_seqlens)
+        ctx.meta = (max_seqlen, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from genrec_amd import ops
+
+        q, k, v, out, lse, cu_seqlens = ctx.saved_tensors
+        max_seqlen, scale = ctx.meta
+        dq, dk, dv = ops.ext().gqa_varlen_bwd(dout, q, k, v, out, lse,
+                                              cu_seqlens, max_seqlen, scale)
+        return dq, dk, dv, None, None, None
+
+
+def gqa_varlen_supported(q: Tensor, k: Tensor, v: Tensor,
+                         cu_seqlens: Tensor) -> bool:
+    """True iff gqa_varlen_attention would run the HIP kernel on these
+    inputs (GPU, bf16 [T,H,D], D in {64,128}, Hq % Hkv == 0, cu_seqlens on
+    the same device, not disabled)."""
+    if os.environ.get("GENREC_DISABLE_ATTN_GQA", "0") == "1":
+        return False
+    if not (q.dim() == 3 and k.dim() == 3 and v.dim() == 3
+            and cu_seqlens.dim() == 1 and cu_seqlens.numel() >= 1):
+        return False
+    if not (q.dtype == k.dtype == v.dtype == torch.bfloat16):
+        return False
+    if cu_seqlens.is_floating_point() or cu_seqlens.device != q.device:
+        return False
+    if q.size(2) not in GQA_HEAD_DIMS or k.size(2) != q.size(2) \
+            or v.shape != k.shape or k.size(0) != q.size(0):
+        return False
+    if k.size(1) == 0 or q.size(1) % k.size(1) != 0:
+        return False
+    return _kernel_available("gqa_varlen_fwd", q, k, v)
+
+
+def gqa_varlen_attention(
+    q: Tensor,  # [T, Hq, D]
+    k: Tensor,  # [T, Hkv, D]
+    v: Tensor,  # [T, Hkv, D]
+    cu_seqlens: Tensor,  # [S+1] int32 on q's device
+    max_seqlen: int,
+    *,
+    scale: float,
+) -> Tensor:
+    """Causal grouped-query self-attention over S packed sequences
+    -> [T, Hq, D] (padding-free training).
+
+    Sequence s owns tokens [cu_seqlens[s], cu_seqlens[s+1]) and attends
+    only to itself; tokens beyond cu_seqlens[-1] and empty sequences give
+    0 and zero gradients. max_seqlen (a host int, >= the longest sequence)
+    only sizes the launch grid and cu_seqlens is never read on the host.
+    Per sequence the result is bit-identical to gqa_flash_attention on that
+    sequence alone. q/k/v may be column slices of a fused projection.
+    """
+    if gqa_varlen_supported(q, k, v, cu_seqlens):
+        cu = cu_seqlens.to(torch.int32).contiguous()
+        return _GqaVarlenAttnFn.apply(q, k, v, cu, int(max_seqlen),
+                                      float(scale))
+    return eager.gqa_varlen_attention(q, k, v, cu_seqlens, max_seqlen,
+                                      scale=scale)
+
+
 BEAM_MAX_SUFFIX = 16   # suffix slots the decode kernel unrolls over
 
 

@@ -134,6 +134,47 @@ def gqa_attention(
     return out.to(q.dtype)
 
 
+def gqa_varlen_attention(
+    q: Tensor,  # [T, Hq, D]
+    k: Tensor,  # [T, Hkv, D]
+    v: Tensor,  # [T, Hkv, D]
+    cu_seqlens: Tensor,  # [S+1] int, sequence s = tokens [cu[s], cu[s+1])
+    max_seqlen: int = 0,  # unused: the mask is built from cu_seqlens
+    *,
+    scale: float,
+) -> Tensor:
+    """Causal grouped-query attention over packed sequences, fp32 math
+    -> [T, Hq, D].
+
+    Token i sees the tokens j <= i of its own sequence (a block-diagonal
+    causal mask built from cu_seqlens on the device, no host sync). Tokens
+    of no sequence (beyond cu[S], before cu[0]) and so empty sequences
+    return 0 and have zero gradients.
+    """
+    T, Hq, D = q.shape
+    Hkv = k.size(1)
+    if Hq % Hkv != 0:
+        raise ValueError(f"Hq={Hq} is not a multiple of Hkv={Hkv}")
+    g = Hq // Hkv
+    cu = cu_seqlens.to(device=q.device, dtype=torch.long)
+    tok = torch.arange(T, device=q.device)
+    # sequence of token t: how many sequence ends are <= t
+    seg = torch.bucketize(tok, cu[1:].contiguous(), right=True)
+    live = (seg < cu.numel() - 1) & (tok >= cu[0])
+    visible = (seg[:, None] == seg[None, :]) & (tok[None, :] <= tok[:, None]) \
+        & live[:, None] & live[None, :]
+    qf = q.float().reshape(T, Hkv, g, D)
+    kf, vf = k.float(), v.float()
+    scores = torch.einsum("qkgd,lkd->kgql", qf, kf) * scale
+    any_visible = live[:, None]                      # the diagonal
+    scores = scores.masked_fill(~visible, float("-inf"))
+    scores = torch.where(any_visible, scores, torch.zeros_like(scores))
+    probs = torch.softmax(scores, dim=-1)
+    probs = torch.where(any_visible, probs, torch.zeros_like(probs))
+    out = torch.einsum("kgql,lkd->qkgd", probs, vf)
+    return out.reshape(T, Hq, D).contiguous().to(q.dtype)
+
+
 def beam_kv_expand(k_pre: Tensor, v_pre: Tensor, k_suf: Tensor,
                    v_suf: Tensor, anc: Tensor, t: int,
                    pre_pad: Optional[Tensor] = None):

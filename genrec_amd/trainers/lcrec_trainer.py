@@ -44,7 +44,21 @@ class ConstrainedDecodingHelper:
 
 
 def sft_collate(batch: List[Dict], model: LCRec, max_len: int = 512,
-                for_generation: bool = False) -> Dict[str, torch.Tensor]:
+                for_generation: bool = False, packing: bool = False,
+                pad_to_multiple_of: int = 64) -> Dict[str, torch.Tensor]:
+    """Right-padded [B,L] SFT batch (left-padded prompts for generation).
+
+    packing=True (SFT only) concatenates the samples into one [1,T] row
+    instead: position_ids restart at every sample, cu_seq_lens (int32
+    [S+1]) holds the sample offsets and max_length the longest sample. T is
+    rounded up to pad_to_multiple_of with pad tokens that lie beyond
+    cu_seq_lens[-1] (labels -100, position 0). Every sample's first label
+    is -100, so no sample's last token predicts the next sample's first;
+    the supervised tokens are otherwise those of the padded batch.
+    """
+    if packing and for_generation:
+        raise ValueError("sft_collate: packing is for SFT batches, not "
+                         "generation")
     tok = model.tokenizer
     input_ids, labels, attn = [], [], []
     metas = []
@@ -60,8 +74,10 @@ def sft_collate(batch: List[Dict], model: LCRec, max_len: int = 512,
         lab = ([-100] * len(p_ids) + r_ids)[:max_len]
         input_ids.append(ids)
         labels.append(lab)
-    max_l = max(len(x) for x in input_ids)
     pad = tok.pad_token_id
+    if packing:
+        return _pack_rows(input_ids, labels, pad, pad_to_multiple_of)
+    max_l = max(len(x) for x in input_ids)
     out_ids, out_attn, out_lab = [], [], []
     for i, ids in enumerate(input_ids):
         n_pad = max_l - len(ids)
@@ -81,6 +97,29 @@ def sft_collate(batch: List[Dict], model: LCRec, max_len: int = 512,
     else:
         res["meta"] = metas
     return res
+
+
+def _pack_rows(input_ids: List[List[int]], labels: List[List[int]],
+               pad: int, multiple: int) -> Dict:
+    flat_ids, flat_lab, pos, cu = [], [], [], [0]
+    for ids, lab in zip(input_ids, labels):
+        flat_ids.extend(ids)
+        flat_lab.extend([-100] + lab[1:] if lab else lab)
+        pos.extend(range(len(ids)))
+        cu.append(len(flat_ids))
+    multiple = max(int(multiple), 1)
+    n_pad = -len(flat_ids) % multiple
+    if not flat_ids:
+        n_pad = multiple
+    return {
+        "input_ids": torch.tensor([flat_ids + [pad] * n_pad],
+                                  dtype=torch.long),
+        "labels": torch.tensor([flat_lab + [-100] * n_pad],
+                               dtype=torch.long),
+        "position_ids": torch.tensor([pos + [0] * n_pad], dtype=torch.long),
+        "cu_seq_lens": torch.tensor(cu, dtype=torch.int32),
+        "max_length": max(len(x) for x in input_ids),
+    }
 
 
 SEM_ID_RE = re.compile(r"<C(\d+)_(\d+)>")
@@ -262,6 +301,9 @@ def train(
     # None = expanded, reordered KV cache in generate_topk; "shared_prefix"
     # = one prompt copy + per-beam suffix slots (needs "genrec_gqa")
     beam_cache: Optional[str] = None,
+    # True = padding-free SFT: each batch's samples packed into one [1,T]
+    # row (needs "genrec_gqa"); evaluation and generation stay left-padded
+    packing: bool = False,
 ):
     if max_length is not None:
         max_seq_len = max_length
@@ -310,7 +352,7 @@ def train(
     valid_ds = mk("valid", max_eval_samples)
 
     helper = ConstrainedDecodingHelper(model, n_codebooks, codebook_size)
-    coll = lambda b: sft_collate(b, model, max_seq_len)
+    coll = lambda b: sft_collate(b, model, max_seq_len, packing=packing)
     gcoll = lambda b: sft_collate(b, model, max_seq_len, for_generation=True)
     train_loader = common.make_loader(train_ds, batch_size, ctx, True, coll,
                                       num_workers=num_workers, seed=seed,
@@ -353,7 +395,8 @@ def train(
             train_loader.sampler.set_epoch(epoch)
         opt.zero_grad(set_to_none=False)
         for it, batch in enumerate(train_loader):
-            batch = {k: v.to(device) for k, v in batch.items()}
+            batch = {k: v.to(device) if torch.is_tensor(v) else v
+                     for k, v in batch.items()}
             micro = (it + 1) % gradient_accumulate_every == 0
             reducer.skip_sync = not micro
             with amp_ctx:

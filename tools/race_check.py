@@ -128,6 +128,24 @@ def build_cases():
         return ops.ext().gqa_attn_bwd(doutg, qg, kg, vg, go, glse, padg,
                                       sg, True)
 
+    # the same kernels in variable-length mode: the B rows above packed
+    # into one [T,H,D] row whose sequence starts sit off the tile grid,
+    # with an empty sequence and a tail that belongs to no sequence
+    Tv = B * Lg
+    qv, kv_, vv, doutv = (t.transpose(1, 2).reshape(Tv, -1, Dg)
+                          for t in (qg, kg, vg, doutg.transpose(1, 2)))
+    cuv = torch.tensor([0, 1, 70, 70, 200, Tv - 50], dtype=torch.int32,
+                       device=dev)
+
+    def gqa_varlen_fwd():
+        return ops.ext().gqa_varlen_fwd(qv, kv_, vv, cuv, Tv, sg)
+
+    vo, vlse = ops.ext().gqa_varlen_fwd(qv, kv_, vv, cuv, Tv, sg)
+
+    def gqa_varlen_bwd():
+        return ops.ext().gqa_varlen_bwd(doutv, qv, kv_, vv, vo, vlse, cuv,
+                                        Tv, sg)
+
     # shared-prefix beam decode: 14 query heads on 2 KV heads x 10 beams =
     # 70 packed rows (two Q tiles), three K tiles over 2 splits, left
     # padding, 3 live suffix slots with a shared ancestor
@@ -241,6 +259,8 @@ def build_cases():
         # no atomics anywhere: bitwise
         ("gqa_attn_fwd", gqa_fwd, 0.0),
         ("gqa_attn_bwd", gqa_bwd, 0.0),
+        ("gqa_varlen_fwd", gqa_varlen_fwd, 0.0),
+        ("gqa_varlen_bwd", gqa_varlen_bwd, 0.0),
         ("beam_attn_fwd", beam_fwd, 0.0),
         ("rms_norm", rms, 0.0),
         ("layer_norm_fwd", ln_fwd, 0.0),
