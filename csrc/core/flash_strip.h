@@ -1,0 +1,241 @@
+// Strip-level steps of a flash-attention tile, one level above mfma_tile.h
+// (attention_gqa, attention_beam).
+//
+// A block of four waves works on 64-row tiles; a wave owns a strip of 16
+// tile rows and holds, per 16-column fragment f, the C fragment
+// acc[f][r] = element (row + r, f*16 + col) of its strip (Strip below).
+// What a wave does with its strip is written here once: the strip x tile
+// MFMA products, the key-validity columns of a K tile, exact (-inf)
+// masking, the guarded running softmax, the P stash and the row store of a
+// finished strip. The head dim D and every row stride are compile-time;
+// staging, barriers and what a kernel iterates over stay with the kernel.
+//
+// Bit-stability: every accumulator here is summed in one fixed order (f
+// outer, kk inner; the reductions as written), so two kernels that call
+// the same step on the same data get the same bits.
+#pragma once
+
+#include "mfma_tile.h"
+
+namespace genrec {
+
+// One bf16 operand as a kernel takes it: base pointer plus batch / head /
+// row strides in elements, d innermost (stride 1).
+struct FlashView {
+  const __hip_bfloat16* p;
+  int64_t b, h, l;
+};
+
+// Where a lane sits in its wave's strip.
+struct Strip {
+  int lane;
+  int row0;  // first tile row of the strip
+  int col;   // the lane's C-fragment column (within a 16-column fragment)
+  int row;   // tile row of the lane's C-fragment register r is row + r
+  __device__ __forceinline__ explicit Strip(int tid)
+      : lane(tid & 63),
+        row0((tid >> 6) * 16),
+        col(frag_col(lane)),
+        row(row0 + frag_row0(lane)) {}
+};
+
+// acc[f] += A[strip rows, 0..K) . B[rows f*16.., 0..K)^T for f < NF; a and b
+// are swizzled tiles with RSA / RSB bytes per row.
+template <int K, int NF, int RSA, int RSB>
+__device__ __forceinline__ void strip_mma(float4v (&acc)[NF], const char* a,
+                                          const char* b, const Strip& w) {
+#pragma unroll
+  for (int f = 0; f < NF; ++f) {
+#pragma unroll
+    for (int kk = 0; kk < K; kk += 32) {
+      acc[f] = mfma_bf16(frag_load(a, w.row0, kk, w.lane, RSA),
+                         frag_load(b, f * 16, kk, w.lane, RSB), acc[f]);
+    }
+  }
+}
+
+// Two strip products with the two MFMAs of one (f, kk) step issued back to
+// back, so each hides the other's operand loads. Per accumulator the
+// summation order is strip_mma's.
+template <int K, int NF, int RS>
+__device__ __forceinline__ void strip_mma2(float4v (&acc1)[NF], const char* a1,
+                                           const char* b1,
+                                           float4v (&acc2)[NF], const char* a2,
+                                           const char* b2, const Strip& w) {
+#pragma unroll
+  for (int f = 0; f < NF; ++f) {
+#pragma unroll
+    for (int kk = 0; kk < K; kk += 32) {
+      acc1[f] = mfma_bf16(frag_load(a1, w.row0, kk, w.lane, RS),
+                          frag_load(b1, f * 16, kk, w.lane, RS), acc1[f]);
+      acc2[f] = mfma_bf16(frag_load(a2, w.row0, kk, w.lane, RS),
+                          frag_load(b2, f * 16, kk, w.lane, RS), acc2[f]);
+    }
+  }
+}
+
+// The lane's four key columns of the K tile at kt0: absolute index, and
+// whether the key exists and is not padded. pad is null or the [Lk] pad row
+// of this batch item.
+struct KeyCols {
+  int j[4];
+  bool ok[4];
+};
+__device__ __forceinline__ KeyCols key_cols(int kt0, int Lk,
+                                            const bool* __restrict__ pad,
+                                            const Strip& w) {
+  KeyCols kc;
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    kc.j[f] = kt0 + f * 16 + w.col;
+    kc.ok[f] = kc.j[f] < Lk;
+    if (kc.ok[f] && pad) kc.ok[f] = !pad[kc.j[f]];
+  }
+  return kc;
+}
+
+// Which (query row, key) pairs are visible. KeyMask: every valid key, for
+// queries that all sit behind the keys. CausalMask: the strip of the Q tile
+// at q0, rows beyond Lq see nothing, and with causal set query row i sits
+// at absolute position i + off.
+struct KeyMask {
+  __device__ __forceinline__ bool operator()(const KeyCols& kc, int f,
+                                             int) const {
+    return kc.ok[f];
+  }
+};
+struct CausalMask {
+  int i0, Lq, off;  // i0: absolute query row of the lane's register 0
+  bool causal;
+  __device__ __forceinline__ CausalMask(int q0, int Lq, int Lk, bool causal,
+                                        const Strip& w)
+      : i0(q0 + w.row), Lq(Lq), off(Lk - Lq), causal(causal) {}
+  __device__ __forceinline__ bool operator()(const KeyCols& kc, int f,
+                                             int r) const {
+    const int i = i0 + r;
+    return kc.ok[f] && i < Lq && !(causal && kc.j[f] > i + off);
+  }
+  // end of the keys the Q tile at q0 can see: K tiles wholly beyond its
+  // diagonal are skipped
+  __device__ __forceinline__ int kt_end(int q0, int Lk) const {
+    return causal ? min(Lk, q0 + TILE + off) : Lk;
+  }
+};
+
+// Running softmax of the lane's four strip rows over the K tiles seen so far.
+struct RunningSoftmax {
+  float m[4], l[4];
+  __device__ __forceinline__ RunningSoftmax() {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { m[r] = -INFINITY; l[r] = 0.f; }
+  }
+
+  // s: the masked scores of one K tile (-inf = masked); comes back as the
+  // unnormalised p. Rescales accO to the new maximum. A row whose keys so
+  // far are all masked keeps m = -inf, l = 0 and contributes nothing (no
+  // exp(-inf - -inf)).
+  template <int NF>
+  __device__ __forceinline__ void step(float (&s)[4][4],
+                                       float4v (&accO)[NF]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float tmax = grp16_max(fmaxf(fmaxf(s[0][r], s[1][r]),
+                                   fmaxf(s[2][r], s[3][r])));
+      float m_new = fmaxf(m[r], tmax);
+      bool dead = (m_new == -INFINITY);
+      float a = (dead || m[r] == -INFINITY) ? (dead ? 1.f : 0.f)
+                                            : __expf(m[r] - m_new);
+      float sum = 0.f;
+#pragma unroll
+      for (int f = 0; f < 4; ++f) {
+        float p = (s[f][r] == -INFINITY) ? 0.f : __expf(s[f][r] - m_new);
+        s[f][r] = p;
+        sum += p;
+      }
+      l[r] = l[r] * a + grp16_sum(sum);
+      m[r] = m_new;
+#pragma unroll
+      for (int f = 0; f < NF; ++f) accO[f][r] *= a;
+    }
+  }
+
+  // normalised finish: out = accO * inv, lse; both 0 for a row that saw no key
+  __device__ __forceinline__ float inv(int r) const {
+    return (l[r] > 0.f) ? 1.0f / l[r] : 0.f;
+  }
+  __device__ __forceinline__ float lse(int r) const {
+    return (l[r] > 0.f) ? m[r] + __logf(l[r]) : 0.f;
+  }
+  // raw finish (split-KV): the partial is (m, l, accO) as they stand; an
+  // empty one has nothing in accO worth storing
+  __device__ __forceinline__ bool empty(int r) const {
+    return m[r] == -INFINITY;
+  }
+};
+
+// Row-major stash of fragment f of the wave's strip as bf16 into a [64][64]
+// tile: x[r] is element (row + r, f*16 + col). The strip is read back by the
+// same wave as an A operand, so a wave barrier suffices.
+__device__ __forceinline__ void strip_stash(char* tile, int f,
+                                            const float (&x)[4],
+                                            const Strip& w) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    tile_store(tile, w.row + r, f * 16 + w.col, bf16_bits(x[r]));
+  }
+}
+
+// The K tile at kt0 of a flash forward for the wave's strip: S = Q K_t^T
+// from the staged qs [64][D] and ks [64][D], exact masking (keys at or
+// beyond Lk, pad keys, and what visible hides), the running-softmax step,
+// and accO += P V_t through the wave's rows of ps [64][64] and vt [D][64].
+template <int D, typename Mask>
+__device__ __forceinline__ void flash_fwd_tile(
+    const char* qs, const char* ks, const char* vt, char* ps, int kt0, int Lk,
+    const bool* __restrict__ pad, const Mask& visible, float scale,
+    RunningSoftmax& sm, float4v (&accO)[D / 16], const Strip& w) {
+  float4v acc[4] = {};
+  strip_mma<D, 4, D * 2, D * 2>(acc, qs, ks, w);
+
+  const KeyCols kc = key_cols(kt0, Lk, pad, w);
+  float s[4][4];
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      s[f][r] = visible(kc, f, r) ? __fmul_rn(acc[f][r], scale) : -INFINITY;
+    }
+  }
+  sm.step(s, accO);
+
+#pragma unroll
+  for (int f = 0; f < 4; ++f) strip_stash(ps, f, s[f], w);
+  __builtin_amdgcn_wave_barrier();
+  strip_mma<TILE, D / 16, 128, 128>(accO, ps, vt, w);
+  __builtin_amdgcn_wave_barrier();
+}
+
+// Store the live rows of a finished strip as bf16 into a [rows, H, D]
+// tensor: tile row t of the tile at i0 goes to row tok0 + i0 + t, head h,
+// while i0 + t < L. mul, when given, scales register row r by mul[r].
+template <int D>
+__device__ __forceinline__ void strip_store(__hip_bfloat16* __restrict__ dst,
+                                            int64_t tok0, int H, int h,
+                                            int i0, int L,
+                                            const float4v (&acc)[D / 16],
+                                            const Strip& w,
+                                            const float* mul = nullptr) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int i = i0 + w.row + r;
+    if (i >= L) continue;
+    const int64_t ob = ((tok0 + i) * H + h) * D;
+#pragma unroll
+    for (int f = 0; f < D / 16; ++f) {
+      const float x = mul ? acc[f][r] * mul[r] : acc[f][r];
+      dst[ob + f * 16 + w.col] = __float2bfloat16(x);
+    }
+  }
+}
+
+}  // namespace genrec

@@ -1,6 +1,9 @@
 // Tile primitives shared by the v_mfma_f32_16x16x32_bf16 kernels
 // (attention_mfma, attention_flash, hstu_attn, attention_gqa, attention_beam,
-// skinny_gemm).
+// skinny_gemm). This header stops at fragment level; the strip-level steps
+// of a flash tile that attention_gqa and attention_beam share (strip
+// products, key columns, masking, running softmax, P stash, row store) are
+// built on it in flash_strip.h.
 //
 // LDS image: a tile is 64 rows of bf16 with 128-byte rows (64 columns) or
 // 256-byte rows (128 columns), stored with an XOR swizzle on 16-byte slots

@@ -8,11 +8,11 @@
 //     the W*g query rows that read one (prompt, KV head) are packed into
 //     64-row Q tiles (row r = w*g + gq is beam w, query head hk*g + gq), so
 //     a prompt K/V tile is staged once per (prompt, KV head, Q tile) instead
-//     of once per (beam, query head). Same tiles, MFMA loop, exact -inf
-//     masking and running-softmax guards as gqa_fwd_kernel, no causal test
-//     (every prefix key precedes every decode query). The K tiles are split
-//     over blockIdx.y; each split writes an unnormalised fp32 partial
-//     (m, l, acc[D]) per row.
+//     of once per (beam, query head). A K tile is processed by the same
+//     flash_fwd_tile step (core/flash_strip.h) as in gqa_fwd_kernel, with
+//     the key-only mask: no causal test, every prefix key precedes every
+//     decode query. The K tiles are split over blockIdx.y; each split
+//     writes an unnormalised fp32 partial (m, l, acc[D]) per row.
 //   * a suffix phase over the generated tokens: row (w, gq) sees the t keys
 //     k_suf[b, s, anc[b,w,s], hk, :], s < t. They differ per beam, so this
 //     is plain VALU work, one wave per output row, in the combine kernel.
@@ -24,10 +24,9 @@
 // Padded prefix keys are staged as zeros, so whatever they hold (NaN
 // included) cannot reach the output through 0 * x.
 
-#include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
-#include "../core/mfma_tile.h"
+#include "../core/attn_host.h"
 
 namespace genrec {
 
@@ -39,16 +38,13 @@ constexpr int BEAM_MAX_T = 16;
 
 template <int D>
 __global__ void __launch_bounds__(256)
-beam_prefix_kernel(const __hip_bfloat16* __restrict__ q,   // [B*W,Hq,1,D]
-                   const __hip_bfloat16* __restrict__ k,   // [B,Hkv,Lp,D]
-                   const __hip_bfloat16* __restrict__ v,
-                   const bool* __restrict__ pre_pad,       // null | [B,Lp]
-                   float* __restrict__ ws_ml,   // [splits, rows, 2]
-                   float* __restrict__ ws_acc,  // [splits, rows, D]
+beam_prefix_kernel(FlashView q,                       // [B*W,Hq,1,D]
+                   FlashView k, FlashView v,          // [B,Hkv,Lp,D]
+                   const bool* __restrict__ pre_pad,  // null | [B,Lp]
+                   float* __restrict__ ws_ml,         // [splits, rows, 2]
+                   float* __restrict__ ws_acc,        // [splits, rows, D]
                    int W, int Hq, int Hkv, int Lp, int qtiles,
-                   int64_t rows_total, float scale, int64_t q_sb, int64_t q_sh,
-                   int64_t k_sb, int64_t k_sh, int64_t k_sl,
-                   int64_t v_sb, int64_t v_sh, int64_t v_sl) {
+                   int64_t rows_total, float scale) {
   constexpr int RS = D * 2;
   const int g = Hq / Hkv;
   const int n_rows = W * g;  // rows of this (prompt, KV head)
@@ -58,11 +54,7 @@ beam_prefix_kernel(const __hip_bfloat16* __restrict__ q,   // [B*W,Hq,1,D]
   const int split = blockIdx.y;
 
   const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int col_base = frag_col(lane);
-  const int row_grp = frag_row0(lane);
-  const int strip = wid * 16;
+  const Strip w(tid);
 
   // this split's K tiles
   const int nkt = (Lp + TILE - 1) / TILE;
@@ -74,16 +66,16 @@ beam_prefix_kernel(const __hip_bfloat16* __restrict__ q,   // [B*W,Hq,1,D]
   int64_t ws_row[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    int rr = qt * TILE + strip + row_grp + r;
-    int w = rr / g, gq = rr % g;
+    int rr = qt * TILE + w.row + r;
+    int beam = rr / g, gq = rr % g;
     ws_row[r] = rr < n_rows
         ? (int64_t)split * rows_total +
-              ((int64_t)b * W + w) * Hq + hk * g + gq
+              ((int64_t)b * W + beam) * Hq + hk * g + gq
         : -1;
   }
 
   if (kt_begin >= kt_end) {  // empty split: an empty state, acc never read
-    if (col_base == 0) {
+    if (w.col == 0) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         if (ws_row[r] < 0) continue;
@@ -105,114 +97,41 @@ beam_prefix_kernel(const __hip_bfloat16* __restrict__ q,   // [B*W,Hq,1,D]
     int row = idx / (D / 8);
     int d0 = (idx % (D / 8)) * 8;
     int rr = qt * TILE + row;
-    int w = rr / g, gq = rr % g;
+    int beam = rr / g, gq = rr % g;
     short8v val = load8(
-        q, ((int64_t)b * W + w) * q_sb + (int64_t)(hk * g + gq) * q_sh + d0,
+        q.p, ((int64_t)b * W + beam) * q.b + (int64_t)(hk * g + gq) * q.h + d0,
         rr < n_rows);
     tile_store(qs, row, d0, val, RS);
   }
 
-  float m_row[4], l_row[4];
-  float4v accO[D / 16];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) { m_row[r] = -INFINITY; l_row[r] = 0.f; }
-#pragma unroll
-  for (int f = 0; f < D / 16; ++f) accO[f] = float4v{0, 0, 0, 0};
+  RunningSoftmax sm;
+  float4v accO[D / 16] = {};
 
-  const __hip_bfloat16* kb = k + (int64_t)b * k_sb + (int64_t)hk * k_sh;
-  const __hip_bfloat16* vb = v + (int64_t)b * v_sb + (int64_t)hk * v_sh;
+  const __hip_bfloat16* kb = k.p + (int64_t)b * k.b + (int64_t)hk * k.h;
+  const __hip_bfloat16* vb = v.p + (int64_t)b * v.b + (int64_t)hk * v.h;
   const bool* pad = pre_pad ? pre_pad + (int64_t)b * Lp : nullptr;
 
   for (int kt0 = kt_begin; kt0 < kt_end; kt0 += TILE) {
     __syncthreads();  // previous iteration's ks/vt fully consumed
-    gstage<D, true, false>(kb, k_sl, kt0, Lp, ks, nullptr, tid, pad);
-    gstage<D, false, true>(vb, v_sl, kt0, Lp, nullptr, vt, tid, pad);
+    gstage<D, true, false>(kb, k.l, kt0, Lp, ks, nullptr, tid, pad);
+    gstage<D, false, true>(vb, v.l, kt0, Lp, nullptr, vt, tid, pad);
     __syncthreads();
-
-    // ---- S = Q K_t^T
-    float4v acc[4];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      acc[f] = float4v{0, 0, 0, 0};
-#pragma unroll
-      for (int kk = 0; kk < D; kk += 32) {
-        acc[f] = mfma_bf16(frag_load(qs, strip, kk, lane, RS),
-                           frag_load(ks, f * 16, kk, lane, RS), acc[f]);
-      }
-    }
-
-    // ---- exact masking (-inf) of pad keys and of j >= Lp
-    float s_val[4][4];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      int j = kt0 + f * 16 + col_base;
-      bool jok = j < Lp;
-      if (jok && pad) jok = !pad[j];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        s_val[f][r] = jok ? __fmul_rn(acc[f][r], scale) : -INFINITY;
-      }
-    }
-
-    // ---- running softmax; a row whose keys so far are all masked keeps
-    // m = -inf, l = 0 and contributes nothing (no exp(-inf - -inf))
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float tmax = grp16_max(fmaxf(fmaxf(s_val[0][r], s_val[1][r]),
-                                   fmaxf(s_val[2][r], s_val[3][r])));
-      float m_new = fmaxf(m_row[r], tmax);
-      bool dead = (m_new == -INFINITY);
-      float a = (dead || m_row[r] == -INFINITY) ? (dead ? 1.f : 0.f)
-                                                : __expf(m_row[r] - m_new);
-      float sum = 0.f;
-#pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        float p = (s_val[f][r] == -INFINITY) ? 0.f
-                                             : __expf(s_val[f][r] - m_new);
-        s_val[f][r] = p;  // reuse as unnormalized p
-        sum += p;
-      }
-      l_row[r] = l_row[r] * a + grp16_sum(sum);
-      m_row[r] = m_new;
-#pragma unroll
-      for (int f = 0; f < D / 16; ++f) accO[f][r] *= a;
-    }
-
-    // ---- stash P (this wave's 16 rows only)
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        tile_store(ps, strip + row_grp + r, f * 16 + col_base,
-                   bf16_bits(s_val[f][r]));
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-
-    // ---- accO += P V_t
-#pragma unroll
-    for (int f = 0; f < D / 16; ++f) {
-#pragma unroll
-      for (int kk = 0; kk < TILE; kk += 32) {
-        accO[f] = mfma_bf16(frag_load(ps, strip, kk, lane),
-                            frag_load(vt, f * 16, kk, lane), accO[f]);
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
+    flash_fwd_tile<D>(qs, ks, vt, ps, kt0, Lp, pad, KeyMask(), scale, sm, accO,
+                      w);
   }
 
   // ---- unnormalised partial of the live rows
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     if (ws_row[r] < 0) continue;
-    if (col_base == 0) {
-      ws_ml[ws_row[r] * 2] = m_row[r];
-      ws_ml[ws_row[r] * 2 + 1] = l_row[r];
+    if (w.col == 0) {
+      ws_ml[ws_row[r] * 2] = sm.m[r];
+      ws_ml[ws_row[r] * 2 + 1] = sm.l[r];
     }
-    if (m_row[r] == -INFINITY) continue;  // empty state: acc never read
+    if (sm.empty(r)) continue;  // empty state: acc never read
 #pragma unroll
     for (int f = 0; f < D / 16; ++f) {
-      ws_acc[ws_row[r] * D + f * 16 + col_base] = accO[f][r];
+      ws_acc[ws_row[r] * D + f * 16 + w.col] = accO[f][r];
     }
   }
 }
@@ -238,7 +157,7 @@ __device__ __forceinline__ void beam_fold(float& m, float& l, float (&a)[E],
 // One wave per output row (b, w, h); lane owns E = D/64 adjacent columns.
 template <int D>
 __global__ void __launch_bounds__(256)
-beam_combine_kernel(const __hip_bfloat16* __restrict__ q,      // [B*W,Hq,1,D]
+beam_combine_kernel(FlashView q,                               // [B*W,Hq,1,D]
                     const __hip_bfloat16* __restrict__ k_suf,  // [B,T,W,Hkv,D]
                     const __hip_bfloat16* __restrict__ v_suf,
                     const int* __restrict__ anc,               // [B,W,T]
@@ -246,8 +165,7 @@ beam_combine_kernel(const __hip_bfloat16* __restrict__ q,      // [B*W,Hq,1,D]
                     const float* __restrict__ ws_acc,
                     __hip_bfloat16* __restrict__ out,          // [B*W,1,Hq,D]
                     int W, int Hq, int Hkv, int T, int t, int splits,
-                    int64_t rows_total, float scale,
-                    int64_t q_sb, int64_t q_sh) {
+                    int64_t rows_total, float scale) {
   constexpr int E = D / 64;
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -261,7 +179,7 @@ beam_combine_kernel(const __hip_bfloat16* __restrict__ q,      // [B*W,Hq,1,D]
 
   float qv[E];
   {
-    const __hip_bfloat16* qp = q + bw * q_sb + (int64_t)h * q_sh + d0;
+    const __hip_bfloat16* qp = q.p + bw * q.b + (int64_t)h * q.h + d0;
 #pragma unroll
     for (int e = 0; e < E; ++e) qv[e] = to_f32(qp[e]);
   }
@@ -330,13 +248,6 @@ beam_combine_kernel(const __hip_bfloat16* __restrict__ q,      // [B*W,Hq,1,D]
 
 // ------------------------------------------------------------------ hosts
 
-// d innermost, 16-byte aligned rows
-bool beam_ok_strides(const torch::Tensor& t, bool with_rows) {
-  return t.stride(3) == 1 && t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0 &&
-         (!with_rows || t.stride(2) % 8 == 0) &&
-         reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
-}
-
 template <int D>
 void beam_launch(const torch::Tensor& q, const torch::Tensor& k,
                  const torch::Tensor& v, const bool* pad,
@@ -349,29 +260,21 @@ void beam_launch(const torch::Tensor& q, const torch::Tensor& k,
   const int g = Hq / Hkv;
   const int qtiles = (W * g + TILE - 1) / TILE;
   const int64_t rows_total = (int64_t)B * W * Hq;
-  const __hip_bfloat16* qp =
-      reinterpret_cast<const __hip_bfloat16*>(q.data_ptr());
+  const FlashView qv = view_bhld(q);  // one row per (beam, head)
   {
     dim3 grid((unsigned int)((int64_t)B * Hkv * qtiles), splits);
     size_t smem = 2 * TILE * D * 2 + D * 128 + TILE * 128;  // 56 KiB at 128
     hipLaunchKernelGGL(beam_prefix_kernel<D>, grid, dim3(256), smem, stream,
-        qp, reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
-        reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()), pad,
-        ws_ml.data_ptr<float>(), ws_acc.data_ptr<float>(), W, Hq, Hkv, Lp,
-        qtiles, rows_total, scale, q.stride(0), q.stride(1),
-        k.stride(0), k.stride(1), k.stride(2),
-        v.stride(0), v.stride(1), v.stride(2));
+        qv, view_bhld(k), view_bhld(v), pad, ws_ml.data_ptr<float>(),
+        ws_acc.data_ptr<float>(), W, Hq, Hkv, Lp, qtiles, rows_total, scale);
     C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   {
     dim3 grid((unsigned int)((rows_total + 3) / 4));
     hipLaunchKernelGGL(beam_combine_kernel<D>, grid, dim3(256), 0, stream,
-        qp, reinterpret_cast<const __hip_bfloat16*>(k_suf.data_ptr()),
-        reinterpret_cast<const __hip_bfloat16*>(v_suf.data_ptr()),
-        anc.data_ptr<int>(), ws_ml.data_ptr<float>(),
-        ws_acc.data_ptr<float>(),
-        reinterpret_cast<__hip_bfloat16*>(out.data_ptr()), W, Hq, Hkv, T, t,
-        splits, rows_total, scale, q.stride(0), q.stride(1));
+        qv, bf16_cptr(k_suf), bf16_cptr(v_suf), anc.data_ptr<int>(),
+        ws_ml.data_ptr<float>(), ws_acc.data_ptr<float>(), bf16_ptr(out), W,
+        Hq, Hkv, T, t, splits, rows_total, scale);
     C10_HIP_KERNEL_LAUNCH_CHECK();
   }
 }
@@ -435,20 +338,18 @@ torch::Tensor beam_attn_fwd(torch::Tensor q, torch::Tensor k_pre,
                   anc.is_contiguous(),
               "beam_attn: anc must be a contiguous int32 [B,W,T]");
   TORCH_CHECK(BW * Hq < (int64_t(1) << 31), "beam_attn: batch too large");
-  torch::Tensor padc;
-  const bool* pad = nullptr;
   if (pre_pad.has_value()) {
     TORCH_CHECK(pre_pad->is_cuda() &&
                     pre_pad->scalar_type() == torch::kBool &&
                     pre_pad->dim() == 2 && pre_pad->size(0) == B &&
                     pre_pad->size(1) == Lp,
                 "beam_attn: pre_pad must be a bool [B,Lp] GPU tensor");
-    padc = pre_pad->contiguous();
-    pad = padc.data_ptr<bool>();
   }
-  torch::Tensor qn = beam_ok_strides(q, false) ? q : q.contiguous();
-  torch::Tensor kn = beam_ok_strides(k_pre, true) ? k_pre : k_pre.contiguous();
-  torch::Tensor vn = beam_ok_strides(v_pre, true) ? v_pre : v_pre.contiguous();
+  torch::Tensor padc;
+  const bool* pad = pad_ptr(pre_pad, padc);
+  // q has one row per (beam, head): only k/v carry a row stride
+  torch::Tensor qn = kernel_readable(q, 2), kn = kernel_readable(k_pre, 3),
+                vn = kernel_readable(v_pre, 3);
 
   const int64_t g = Hq / Hkv;
   int64_t S = splits > 0 ? splits : beam_attn_pick_splits(B, Hkv, W * g, Lp);
@@ -457,13 +358,11 @@ torch::Tensor beam_attn_fwd(torch::Tensor q, torch::Tensor k_pre,
   auto ws_ml = torch::empty({S, BW * Hq, 2}, f32);
   auto ws_acc = torch::empty({S, BW * Hq, D}, f32);
   auto out = torch::empty({BW, 1, Hq, D}, q.options());
-  if (D == 64) {
-    beam_launch<64>(qn, kn, vn, pad, k_suf, v_suf, anc, ws_ml, ws_acc, out,
-                    B, W, Hq, Hkv, Lp, T, t, S, (float)scale);
-  } else {
-    beam_launch<128>(qn, kn, vn, pad, k_suf, v_suf, anc, ws_ml, ws_acc, out,
-                     B, W, Hq, Hkv, Lp, T, t, S, (float)scale);
-  }
+  dispatch_head_dim(D, [&](auto d) {
+    beam_launch<decltype(d)::value>(qn, kn, vn, pad, k_suf, v_suf, anc, ws_ml,
+                                    ws_acc, out, B, W, Hq, Hkv, Lp, T, t, S,
+                                    (float)scale);
+  });
   return out;
 }
 

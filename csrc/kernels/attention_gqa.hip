@@ -4,7 +4,11 @@
 // Same fragment geometry as attention_flash.hip (64-row tiles, four waves
 // that own 16 query rows each, v_mfma_f32_16x16x32_bf16, XOR-swizzled LDS
 // tiles read with 16-byte fragment loads, in-register 8x8 transpose for
-// the transposed operands), with what the LLM case needs on top:
+// the transposed operands). What a wave does with its 16-row strip of a
+// tile (strip products, key columns, masking, running softmax, P stash,
+// row store) is core/flash_strip.h, shared with attention_beam.hip; the
+// kernels here own staging, barriers and their loops. On top of that,
+// what the LLM case needs:
 //
 //   * query head h reads KV head h / g in-kernel (g = Hq / Hkv); K/V are
 //     never expanded
@@ -41,61 +45,70 @@
 // and delta are [Hq,T], dq/dk/dv are [T,H,D]; all are zero-filled by the
 // host, which is what tokens beyond cu[S] and empty sequences keep.
 
-#include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
-#include "../core/mfma_tile.h"
+#include "../core/attn_host.h"
 
 namespace genrec {
 
 namespace {
 
-// Token range of packed sequence s, clamped so that it lies inside [0,T].
-__device__ __forceinline__ void gqa_seq_range(const int* __restrict__ cu,
-                                              int s, int T, int* start,
-                                              int* len) {
-  const int a = min(max(cu[s], 0), T);
-  const int e = min(max(cu[s + 1], a), T);
-  *start = a;
-  *len = e - a;
+// The batch item (fixed-length) or packed sequence (VARLEN) a block works
+// on, and where its rows sit in the operands and outputs.
+template <bool VARLEN>
+struct GqaSeq {
+  int Lq, Lk;  // lengths of this item
+  int b;
+  int start;   // first token of the sequence in the packed tensors
+  bool work;   // false: the block's tile lies beyond the sequence
+  // first row of the item in a [B,L,H,D] | [T,H,D] tensor
+  __device__ __forceinline__ int64_t tok0(int L) const {
+    return VARLEN ? (int64_t)start : (int64_t)b * L;
+  }
+  // first lse / delta entry of head h ([B,Hq,Lq] | [Hq,T])
+  __device__ __forceinline__ int64_t rowb(int h, int Hq, int T) const {
+    return VARLEN ? (int64_t)h * T + start : ((int64_t)b * Hq + h) * Lq;
+  }
+  // row 0 of head h of the item in operand x
+  __device__ __forceinline__ const __hip_bfloat16* rows(const FlashView& x,
+                                                        int h) const {
+    return x.p + (VARLEN ? (int64_t)start * x.l : (int64_t)b * x.b) +
+           (int64_t)h * x.h;
+  }
+};
+
+// tile0: first row of the block's Q (or K) tile. VARLEN reads the token
+// range of sequence b, clamped so that it lies inside [0,T]; work is
+// uniform per block, so a kernel may return on it before its first barrier.
+template <bool VARLEN>
+__device__ __forceinline__ GqaSeq<VARLEN> gqa_seq(const int* __restrict__ cu,
+                                                  int T, int b, int Lq, int Lk,
+                                                  int tile0) {
+  if constexpr (VARLEN) {
+    const int a = min(max(cu[b], 0), T);
+    const int e = min(max(cu[b + 1], a), T);
+    return {e - a, e - a, b, a, tile0 < e - a};
+  } else {
+    return {Lq, Lk, b, 0, true};
+  }
 }
 
 // ------------------------------------------------------------------ forward
 
 template <int D, bool VARLEN>
 __global__ void __launch_bounds__(256)
-gqa_fwd_kernel(const __hip_bfloat16* __restrict__ q,
-               const __hip_bfloat16* __restrict__ k,
-               const __hip_bfloat16* __restrict__ v,
+gqa_fwd_kernel(FlashView q, FlashView k, FlashView v,
                const bool* __restrict__ key_pad,  // null | [B,Lk]
                __hip_bfloat16* __restrict__ out,  // [B,Lq,Hq,D] | [T,Hq,D]
                float* __restrict__ lse,           // [B,Hq,Lq] | [Hq,T]
                int Hq, int Hkv, int Lq, int Lk, float scale, bool causal,
-               int64_t q_sb, int64_t q_sh, int64_t q_sl,
-               int64_t k_sb, int64_t k_sh, int64_t k_sl,
-               int64_t v_sb, int64_t v_sh, int64_t v_sl,
                const int* __restrict__ cu, int T) {  // VARLEN only
   constexpr int RS = D * 2;
   const int b = blockIdx.x / Hq, h = blockIdx.x % Hq;
   const int hk = h / (Hq / Hkv);
   const int q0 = blockIdx.y * TILE;
-  int64_t tok0, rowb;  // first out row of b; first lse entry of (b, h)
-  if constexpr (VARLEN) {
-    int start;
-    gqa_seq_range(cu, b, T, &start, &Lq);
-    Lk = Lq;
-    if (q0 >= Lq) return;  // uniform per block, before any barrier
-    q_sb = k_sb = v_sb = 0;  // the sequence's base is its first token
-    q += (int64_t)start * q_sl;
-    k += (int64_t)start * k_sl;
-    v += (int64_t)start * v_sl;
-    tok0 = start;
-    rowb = (int64_t)h * T + start;
-  } else {
-    tok0 = (int64_t)b * Lq;
-    rowb = ((int64_t)b * Hq + h) * Lq;
-  }
-  const int off = Lk - Lq;  // query row i sits at absolute position i + off
+  const GqaSeq<VARLEN> sq = gqa_seq<VARLEN>(cu, T, b, Lq, Lk, q0);
+  if (!sq.work) return;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* qs = smem;               // [64][D]   Q rows
@@ -104,122 +117,38 @@ gqa_fwd_kernel(const __hip_bfloat16* __restrict__ q,
   char* ps = vt + D * 128;       // [64][64]  P (per tile)
 
   const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int col_base = frag_col(lane);
-  const int row_grp = frag_row0(lane);
-  const int strip = wid * 16;
+  const Strip w(tid);
 
-  gstage<D, true, false>(q + (int64_t)b * q_sb + (int64_t)h * q_sh, q_sl, q0,
-                         Lq, qs, nullptr, tid);
+  gstage<D, true, false>(sq.rows(q, h), q.l, q0, sq.Lq, qs, nullptr, tid);
 
-  float m_row[4], l_row[4];
-  float4v accO[D / 16];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) { m_row[r] = -INFINITY; l_row[r] = 0.f; }
-#pragma unroll
-  for (int f = 0; f < D / 16; ++f) accO[f] = float4v{0, 0, 0, 0};
+  RunningSoftmax sm;
+  float4v accO[D / 16] = {};
 
-  // K tiles wholly beyond the diagonal of this Q tile are skipped
-  int kt_end = Lk;
-  if (causal) kt_end = min(Lk, q0 + TILE + off);
-  const __hip_bfloat16* kb = k + (int64_t)b * k_sb + (int64_t)hk * k_sh;
-  const __hip_bfloat16* vb = v + (int64_t)b * v_sb + (int64_t)hk * v_sh;
+  const CausalMask visible(q0, sq.Lq, sq.Lk, causal, w);
+  const int kt_end = visible.kt_end(q0, sq.Lk);
+  const __hip_bfloat16* kb = sq.rows(k, hk);
+  const __hip_bfloat16* vb = sq.rows(v, hk);
+  const bool* pad = key_pad ? key_pad + (int64_t)b * sq.Lk : nullptr;
 
   for (int kt0 = 0; kt0 < kt_end; kt0 += TILE) {
     __syncthreads();  // previous iteration's ks/vt fully consumed
-    gstage<D, true, false>(kb, k_sl, kt0, Lk, ks, nullptr, tid);
-    gstage<D, false, true>(vb, v_sl, kt0, Lk, nullptr, vt, tid);
+    gstage<D, true, false>(kb, k.l, kt0, sq.Lk, ks, nullptr, tid);
+    gstage<D, false, true>(vb, v.l, kt0, sq.Lk, nullptr, vt, tid);
     __syncthreads();
-
-    // ---- S = Q K_t^T
-    float4v acc[4];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      acc[f] = float4v{0, 0, 0, 0};
-#pragma unroll
-      for (int kk = 0; kk < D; kk += 32) {
-        acc[f] = mfma_bf16(frag_load(qs, strip, kk, lane, RS),
-                           frag_load(ks, f * 16, kk, lane, RS), acc[f]);
-      }
-    }
-
-    // ---- exact masking (-inf)
-    float s_val[4][4];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      int j = kt0 + f * 16 + col_base;
-      bool jok = j < Lk;
-      if (jok && key_pad) jok = !key_pad[(int64_t)b * Lk + j];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int i = q0 + strip + row_grp + r;
-        bool ok = jok && i < Lq && !(causal && j > i + off);
-        s_val[f][r] = ok ? __fmul_rn(acc[f][r], scale) : -INFINITY;
-      }
-    }
-
-    // ---- running softmax; a row whose keys so far are all masked keeps
-    // m = -inf, l = 0 and contributes nothing (no exp(-inf - -inf))
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float tmax = grp16_max(fmaxf(fmaxf(s_val[0][r], s_val[1][r]),
-                                   fmaxf(s_val[2][r], s_val[3][r])));
-      float m_new = fmaxf(m_row[r], tmax);
-      bool dead = (m_new == -INFINITY);
-      float a = (dead || m_row[r] == -INFINITY) ? (dead ? 1.f : 0.f)
-                                                : __expf(m_row[r] - m_new);
-      float sum = 0.f;
-#pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        float p = (s_val[f][r] == -INFINITY) ? 0.f
-                                             : __expf(s_val[f][r] - m_new);
-        s_val[f][r] = p;  // reuse as unnormalized p
-        sum += p;
-      }
-      l_row[r] = l_row[r] * a + grp16_sum(sum);
-      m_row[r] = m_new;
-#pragma unroll
-      for (int f = 0; f < D / 16; ++f) accO[f][r] *= a;
-    }
-
-    // ---- stash P (this wave's 16 rows only)
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        tile_store(ps, strip + row_grp + r, f * 16 + col_base,
-                   bf16_bits(s_val[f][r]));
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-
-    // ---- accO += P V_t
-#pragma unroll
-    for (int f = 0; f < D / 16; ++f) {
-#pragma unroll
-      for (int kk = 0; kk < TILE; kk += 32) {
-        accO[f] = mfma_bf16(frag_load(ps, strip, kk, lane),
-                            frag_load(vt, f * 16, kk, lane), accO[f]);
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
+    flash_fwd_tile<D>(qs, ks, vt, ps, kt0, sq.Lk, pad, visible, scale, sm, accO,
+                      w);
   }
 
-  // ---- finalize
+  float inv[4];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    int i = q0 + strip + row_grp + r;
-    if (i >= Lq) continue;
-    float inv = (l_row[r] > 0.f) ? 1.0f / l_row[r] : 0.f;
-    int64_t ob = ((tok0 + i) * Hq + h) * D;
+  for (int r = 0; r < 4; ++r) inv[r] = sm.inv(r);
+  strip_store<D>(out, sq.tok0(sq.Lq), Hq, h, q0, sq.Lq, accO, w, inv);
+  if (w.col == 0) {
+    const int64_t rowb = sq.rowb(h, Hq, T);
 #pragma unroll
-    for (int f = 0; f < D / 16; ++f) {
-      out[ob + f * 16 + col_base] = __float2bfloat16(accO[f][r] * inv);
-    }
-    if (col_base == 0) {
-      lse[rowb + i] =
-          (l_row[r] > 0.f) ? m_row[r] + __logf(l_row[r]) : 0.f;
+    for (int r = 0; r < 4; ++r) {
+      int i = q0 + w.row + r;
+      if (i < sq.Lq) lse[rowb + i] = sm.lse(r);
     }
   }
 }
@@ -228,11 +157,10 @@ gqa_fwd_kernel(const __hip_bfloat16* __restrict__ q,
 
 template <int D>
 __global__ void __launch_bounds__(256)
-gqa_delta_kernel(const __hip_bfloat16* __restrict__ dout,  // [B,Lq,Hq,D] view
-                 const __hip_bfloat16* __restrict__ out,   // [B,Lq,Hq,D]
-                 float* __restrict__ delta,                // [B,Hq,Lq]
-                 int Hq, int Lq, int64_t n_rows,
-                 int64_t do_sb, int64_t do_sh, int64_t do_sl) {
+gqa_delta_kernel(FlashView dout,                          // [B,Lq,Hq,D] view
+                 const __hip_bfloat16* __restrict__ out,  // [B,Lq,Hq,D]
+                 float* __restrict__ delta,               // [B,Hq,Lq]
+                 int Hq, int Lq, int64_t n_rows) {
   constexpr int GRP = D / 8;  // lanes per row
   const int64_t row = (int64_t)blockIdx.x * (256 / GRP) + threadIdx.x / GRP;
   const int c = (threadIdx.x % GRP) * 8;
@@ -243,7 +171,7 @@ gqa_delta_kernel(const __hip_bfloat16* __restrict__ dout,  // [B,Lq,Hq,D] view
     int h = bh % Hq;
     int64_t b = bh / Hq;
     short8v a = *reinterpret_cast<const short8v*>(
-        &dout[b * do_sb + (int64_t)h * do_sh + (int64_t)i * do_sl + c]);
+        &dout.p[b * dout.b + (int64_t)h * dout.h + (int64_t)i * dout.l + c]);
     short8v o = *reinterpret_cast<const short8v*>(
         &out[((b * Lq + i) * Hq + h) * D + c]);
 #pragma unroll
@@ -257,59 +185,64 @@ gqa_delta_kernel(const __hip_bfloat16* __restrict__ dout,  // [B,Lq,Hq,D] view
   if (row < n_rows && c == 0) delta[row] = acc;
 }
 
-// Recompute P and dS for one 16x64 strip from the S and dP accumulators.
-// p = exp(s - lse) for visible keys, exactly 0 for masked ones. The
-// softmax Jacobian carries p (1 - p): a probability that rounds to 1 (a row
-// with one visible key, e.g. row 0 of every prefill) has dS = 0, where
-// dP - delta would leave the rounding difference between the MFMA dot
-// product and the delta pre-kernel's sum.
-#define GQA_P_DS(f, r, p_out, ds_out)                                      \
-  {                                                                        \
-    int i_ = q0 + strip + row_grp + (r);                                   \
-    bool ok_ = jok[f] && i_ < Lq && !(causal && jcol[f] > i_ + off);       \
-    float s_ = __fmul_rn(acc[f][r], scale); /* as forward: no fma */       \
-    float p_ = ok_ ? __expf(s_ - lse_r[r]) : 0.f;                          \
-    p_out = p_;                                                            \
-    ds_out = (p_ == 1.0f) ? 0.f : p_ * (accp[f][r] - dl_r[r]) * scale;     \
+// ------------------------ backward: what both kernels do after S and dP
+
+// lse and delta of the lane's four rows of the Q tile at q0 (0 beyond Lq)
+struct GqaRowStats {
+  float lse[4], dl[4];
+};
+__device__ __forceinline__ GqaRowStats gqa_row_stats(
+    const float* __restrict__ lse, const float* __restrict__ delta,
+    int64_t rowb, int q0, int Lq, const Strip& w) {
+  GqaRowStats st;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    int i = q0 + w.row + r;
+    st.lse[r] = i < Lq ? lse[rowb + i] : 0.f;
+    st.dl[r] = i < Lq ? delta[rowb + i] : 0.f;
   }
+  return st;
+}
+
+// P and scale*dS of fragment f of a strip, from the strip's S = Q K_t^T
+// (acc) and dP = dO V_t^T (accp) accumulators. p = exp(s - lse) for visible
+// keys, exactly 0 for masked ones. The softmax Jacobian carries p (1 - p): a
+// probability that rounds to 1 (a row with one visible key, e.g. row 0 of
+// every prefill) has dS = 0, where dP - delta would leave the rounding
+// difference between the MFMA dot product and the delta pre-kernel's sum.
+__device__ __forceinline__ void gqa_p_ds(int f, const float4v (&acc)[4],
+                                         const float4v (&accp)[4],
+                                         const KeyCols& kc,
+                                         const CausalMask& visible,
+                                         const GqaRowStats& st, float scale,
+                                         float (&p)[4], float (&ds)[4]) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float s = __fmul_rn(acc[f][r], scale);  // as forward: no fma
+    p[r] = visible(kc, f, r) ? __expf(s - st.lse[r]) : 0.f;
+    ds[r] = (p[r] == 1.0f) ? 0.f : p[r] * (accp[f][r] - st.dl[r]) * scale;
+  }
+}
 
 // ------------------------------------------------------- backward: dK, dV
 
 template <int D, bool VARLEN>
 __global__ void __launch_bounds__(256)
-gqa_bwd_dkdv_kernel(const __hip_bfloat16* __restrict__ dout,
-                    const __hip_bfloat16* __restrict__ q,
-                    const __hip_bfloat16* __restrict__ k,
-                    const __hip_bfloat16* __restrict__ v,
+gqa_bwd_dkdv_kernel(FlashView dout, FlashView q, FlashView k, FlashView v,
                     const float* __restrict__ lse,    // [B,Hq,Lq]
                     const float* __restrict__ delta,  // [B,Hq,Lq]
                     const bool* __restrict__ key_pad,
                     __hip_bfloat16* __restrict__ dk,  // [B,Lk,Hkv,D]
                     __hip_bfloat16* __restrict__ dv,  // [B,Lk,Hkv,D]
                     int Hq, int Hkv, int Lq, int Lk, float scale, bool causal,
-                    int64_t do_sb, int64_t do_sh, int64_t do_sl,
-                    int64_t q_sb, int64_t q_sh, int64_t q_sl,
-                    int64_t k_sb, int64_t k_sh, int64_t k_sl,
-                    int64_t v_sb, int64_t v_sh, int64_t v_sl,
                     const int* __restrict__ cu, int T) {  // VARLEN only
   constexpr int RS = D * 2;
   const int b = blockIdx.x / Hkv, hk = blockIdx.x % Hkv;
   const int grp = Hq / Hkv;
   const int kt0 = blockIdx.y * TILE;
-  int64_t tok0 = (int64_t)b * Lk;  // first dk/dv row of b
-  int start = 0;
-  if constexpr (VARLEN) {
-    gqa_seq_range(cu, b, T, &start, &Lq);
-    Lk = Lq;
-    if (kt0 >= Lk) return;  // uniform per block, before any barrier
-    do_sb = q_sb = k_sb = v_sb = 0;
-    dout += (int64_t)start * do_sl;
-    q += (int64_t)start * q_sl;
-    k += (int64_t)start * k_sl;
-    v += (int64_t)start * v_sl;
-    tok0 = start;
-  }
-  const int off = Lk - Lq;
+  const GqaSeq<VARLEN> sq = gqa_seq<VARLEN>(cu, T, b, Lq, Lk, kt0);
+  if (!sq.work) return;
+  const int off = sq.Lk - sq.Lq;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* ks = smem;                // [64][D]  K_t rows (persistent)
@@ -322,33 +255,15 @@ gqa_bwd_dkdv_kernel(const __hip_bfloat16* __restrict__ dout,
   char* pt = dst + TILE * 128;    // [64 j][64 i]  P^T
 
   const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int col_base = frag_col(lane);
-  const int row_grp = frag_row0(lane);
-  const int strip = wid * 16;
-  const int i0g = strip + row_grp;  // 8-byte aligned store base
+  const Strip w(tid);
 
-  gstage<D, true, false>(k + (int64_t)b * k_sb + (int64_t)hk * k_sh, k_sl,
-                         kt0, Lk, ks, nullptr, tid);
-  gstage<D, true, false>(v + (int64_t)b * v_sb + (int64_t)hk * v_sh, v_sl,
-                         kt0, Lk, vs, nullptr, tid);
+  gstage<D, true, false>(sq.rows(k, hk), k.l, kt0, sq.Lk, ks, nullptr, tid);
+  gstage<D, true, false>(sq.rows(v, hk), v.l, kt0, sq.Lk, vs, nullptr, tid);
 
-  int jcol[4];
-  bool jok[4];
-#pragma unroll
-  for (int f = 0; f < 4; ++f) {
-    jcol[f] = kt0 + f * 16 + col_base;
-    jok[f] = jcol[f] < Lk;
-    if (jok[f] && key_pad) jok[f] = !key_pad[(int64_t)b * Lk + jcol[f]];
-  }
+  const KeyCols kc = key_cols(
+      kt0, sq.Lk, key_pad ? key_pad + (int64_t)b * sq.Lk : nullptr, w);
 
-  float4v acck[D / 16], accv[D / 16];
-#pragma unroll
-  for (int f = 0; f < D / 16; ++f) {
-    acck[f] = float4v{0, 0, 0, 0};
-    accv[f] = float4v{0, 0, 0, 0};
-  }
+  float4v acck[D / 16] = {}, accv[D / 16] = {};
 
   // Q tiles whose every row sits before this K tile see none of it
   int q_begin = 0;
@@ -356,123 +271,65 @@ gqa_bwd_dkdv_kernel(const __hip_bfloat16* __restrict__ dout,
 
   for (int hh = 0; hh < grp; ++hh) {
     const int h = hk * grp + hh;
-    const __hip_bfloat16* qb = q + (int64_t)b * q_sb + (int64_t)h * q_sh;
-    const __hip_bfloat16* dob = dout + (int64_t)b * do_sb + (int64_t)h * do_sh;
-    const int64_t rowb =
-        VARLEN ? (int64_t)h * T + start : ((int64_t)b * Hq + h) * Lq;
-    for (int q0 = q_begin; q0 < Lq; q0 += TILE) {
+    const __hip_bfloat16* qb = sq.rows(q, h);
+    const __hip_bfloat16* dob = sq.rows(dout, h);
+    const int64_t rowb = sq.rowb(h, Hq, T);
+    for (int q0 = q_begin; q0 < sq.Lq; q0 += TILE) {
       __syncthreads();  // previous tile's qs/dos/qt/dot/dst/pt consumed
-      gstage<D, true, true>(qb, q_sl, q0, Lq, qs, qt, tid);
-      gstage<D, true, true>(dob, do_sl, q0, Lq, dos, dot, tid);
+      gstage<D, true, true>(qb, q.l, q0, sq.Lq, qs, qt, tid);
+      gstage<D, true, true>(dob, dout.l, q0, sq.Lq, dos, dot, tid);
       __syncthreads();
 
-      float lse_r[4], dl_r[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int i = q0 + strip + row_grp + r;
-        lse_r[r] = i < Lq ? lse[rowb + i] : 0.f;
-        dl_r[r] = i < Lq ? delta[rowb + i] : 0.f;
-      }
+      const GqaRowStats st = gqa_row_stats(lse, delta, rowb, q0, sq.Lq, w);
+      const CausalMask visible(q0, sq.Lq, sq.Lk, causal, w);
 
       // ---- S = Q K_t^T, dP = dO V_t^T (rows = this wave's q strip)
-      float4v acc[4], accp[4];
-#pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        acc[f] = float4v{0, 0, 0, 0};
-        accp[f] = float4v{0, 0, 0, 0};
-#pragma unroll
-        for (int kk = 0; kk < D; kk += 32) {
-          acc[f] = mfma_bf16(frag_load(qs, strip, kk, lane, RS),
-                             frag_load(ks, f * 16, kk, lane, RS), acc[f]);
-          accp[f] = mfma_bf16(frag_load(dos, strip, kk, lane, RS),
-                              frag_load(vs, f * 16, kk, lane, RS), accp[f]);
-        }
-      }
+      float4v acc[4] = {}, accp[4] = {};
+      strip_mma2<D, 4, RS>(acc, qs, ks, accp, dos, vs, w);
 
-      // ---- P^T and (scale*dS)^T tiles
+      // ---- P^T and (scale*dS)^T tiles: the lane's 4 rows are 4 adjacent
+      // columns of the transposed image, one 8-byte store each
 #pragma unroll
       for (int f = 0; f < 4; ++f) {
+        float p[4], ds[4];
+        gqa_p_ds(f, acc, accp, kc, visible, st, scale, p, ds);
         short4v ppack, dpack;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          float pv, dsv;
-          GQA_P_DS(f, r, pv, dsv);
-          ppack[r] = bf16_bits(pv);
-          dpack[r] = bf16_bits(dsv);
+          ppack[r] = bf16_bits(p[r]);
+          dpack[r] = bf16_bits(ds[r]);
         }
-        int jl = f * 16 + col_base;
-        tile_store(pt, jl, i0g, ppack);
-        tile_store(dst, jl, i0g, dpack);
+        tile_store(pt, f * 16 + w.col, w.row, ppack);
+        tile_store(dst, f * 16 + w.col, w.row, dpack);
       }
       __syncthreads();  // pt/dst complete across waves
 
       // ---- dK_t += (scale*dS)^T Q ; dV_t += P^T dO (rows = k strip)
-#pragma unroll
-      for (int f = 0; f < D / 16; ++f) {
-#pragma unroll
-        for (int kk = 0; kk < TILE; kk += 32) {
-          acck[f] = mfma_bf16(frag_load(dst, strip, kk, lane),
-                              frag_load(qt, f * 16, kk, lane), acck[f]);
-          accv[f] = mfma_bf16(frag_load(pt, strip, kk, lane),
-                              frag_load(dot, f * 16, kk, lane), accv[f]);
-        }
-      }
+      strip_mma2<TILE, D / 16, 128>(acck, dst, qt, accv, pt, dot, w);
     }
   }
 
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    int j = kt0 + strip + row_grp + r;
-    if (j >= Lk) continue;
-    int64_t ob = ((tok0 + j) * Hkv + hk) * D;
-#pragma unroll
-    for (int f = 0; f < D / 16; ++f) {
-      dk[ob + f * 16 + col_base] = __float2bfloat16(acck[f][r]);
-      dv[ob + f * 16 + col_base] = __float2bfloat16(accv[f][r]);
-    }
-  }
+  strip_store<D>(dk, sq.tok0(sq.Lk), Hkv, hk, kt0, sq.Lk, acck, w);
+  strip_store<D>(dv, sq.tok0(sq.Lk), Hkv, hk, kt0, sq.Lk, accv, w);
 }
 
 // ----------------------------------------------------------- backward: dQ
 
 template <int D, bool VARLEN>
 __global__ void __launch_bounds__(256)
-gqa_bwd_dq_kernel(const __hip_bfloat16* __restrict__ dout,
-                  const __hip_bfloat16* __restrict__ q,
-                  const __hip_bfloat16* __restrict__ k,
-                  const __hip_bfloat16* __restrict__ v,
+gqa_bwd_dq_kernel(FlashView dout, FlashView q, FlashView k, FlashView v,
                   const float* __restrict__ lse,
                   const float* __restrict__ delta,
                   const bool* __restrict__ key_pad,
                   __hip_bfloat16* __restrict__ dq,  // [B,Lq,Hq,D]
                   int Hq, int Hkv, int Lq, int Lk, float scale, bool causal,
-                  int64_t do_sb, int64_t do_sh, int64_t do_sl,
-                  int64_t q_sb, int64_t q_sh, int64_t q_sl,
-                  int64_t k_sb, int64_t k_sh, int64_t k_sl,
-                  int64_t v_sb, int64_t v_sh, int64_t v_sl,
                   const int* __restrict__ cu, int T) {  // VARLEN only
   constexpr int RS = D * 2;
   const int b = blockIdx.x / Hq, h = blockIdx.x % Hq;
   const int hk = h / (Hq / Hkv);
   const int q0 = blockIdx.y * TILE;
-  int64_t tok0, rowb;  // first dq row of b; first lse/delta entry of (b, h)
-  if constexpr (VARLEN) {
-    int start;
-    gqa_seq_range(cu, b, T, &start, &Lq);
-    Lk = Lq;
-    if (q0 >= Lq) return;  // uniform per block, before any barrier
-    do_sb = q_sb = k_sb = v_sb = 0;
-    dout += (int64_t)start * do_sl;
-    q += (int64_t)start * q_sl;
-    k += (int64_t)start * k_sl;
-    v += (int64_t)start * v_sl;
-    tok0 = start;
-    rowb = (int64_t)h * T + start;
-  } else {
-    tok0 = (int64_t)b * Lq;
-    rowb = ((int64_t)b * Hq + h) * Lq;
-  }
-  const int off = Lk - Lq;
+  const GqaSeq<VARLEN> sq = gqa_seq<VARLEN>(cu, T, b, Lq, Lk, q0);
+  if (!sq.work) return;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* qs = smem;                // [64][D]  Q rows (persistent)
@@ -483,110 +340,49 @@ gqa_bwd_dq_kernel(const __hip_bfloat16* __restrict__ dout,
   char* dsn = kt + D * 128;       // [64 i][64 j]  scale*dS
 
   const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int col_base = frag_col(lane);
-  const int row_grp = frag_row0(lane);
-  const int strip = wid * 16;
+  const Strip w(tid);
 
-  gstage<D, true, false>(q + (int64_t)b * q_sb + (int64_t)h * q_sh, q_sl, q0,
-                         Lq, qs, nullptr, tid);
-  gstage<D, true, false>(dout + (int64_t)b * do_sb + (int64_t)h * do_sh,
-                         do_sl, q0, Lq, dos, nullptr, tid);
+  gstage<D, true, false>(sq.rows(q, h), q.l, q0, sq.Lq, qs, nullptr, tid);
+  gstage<D, true, false>(sq.rows(dout, h), dout.l, q0, sq.Lq, dos, nullptr,
+                         tid);
 
-  float lse_r[4], dl_r[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    int i = q0 + strip + row_grp + r;
-    lse_r[r] = i < Lq ? lse[rowb + i] : 0.f;
-    dl_r[r] = i < Lq ? delta[rowb + i] : 0.f;
-  }
+  const GqaRowStats st =
+      gqa_row_stats(lse, delta, sq.rowb(h, Hq, T), q0, sq.Lq, w);
 
-  float4v accq[D / 16];
-#pragma unroll
-  for (int f = 0; f < D / 16; ++f) accq[f] = float4v{0, 0, 0, 0};
+  float4v accq[D / 16] = {};
 
-  int kt_end = Lk;
-  if (causal) kt_end = min(Lk, q0 + TILE + off);
-  const __hip_bfloat16* kb = k + (int64_t)b * k_sb + (int64_t)hk * k_sh;
-  const __hip_bfloat16* vb = v + (int64_t)b * v_sb + (int64_t)hk * v_sh;
+  const CausalMask visible(q0, sq.Lq, sq.Lk, causal, w);
+  const int kt_end = visible.kt_end(q0, sq.Lk);
+  const __hip_bfloat16* kb = sq.rows(k, hk);
+  const __hip_bfloat16* vb = sq.rows(v, hk);
+  const bool* pad = key_pad ? key_pad + (int64_t)b * sq.Lk : nullptr;
 
   for (int kt0 = 0; kt0 < kt_end; kt0 += TILE) {
     __syncthreads();  // previous tile's ks/vs/kt consumed
-    gstage<D, true, true>(kb, k_sl, kt0, Lk, ks, kt, tid);
-    gstage<D, true, false>(vb, v_sl, kt0, Lk, vs, nullptr, tid);
+    gstage<D, true, true>(kb, k.l, kt0, sq.Lk, ks, kt, tid);
+    gstage<D, true, false>(vb, v.l, kt0, sq.Lk, vs, nullptr, tid);
     __syncthreads();
 
-    int jcol[4];
-    bool jok[4];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      jcol[f] = kt0 + f * 16 + col_base;
-      jok[f] = jcol[f] < Lk;
-      if (jok[f] && key_pad) jok[f] = !key_pad[(int64_t)b * Lk + jcol[f]];
-    }
+    float4v acc[4] = {}, accp[4] = {};
+    strip_mma2<D, 4, RS>(acc, qs, ks, accp, dos, vs, w);
 
-    float4v acc[4], accp[4];
+    // ---- dQ += (scale*dS) K_t through the wave's rows of dsn
+    const KeyCols kc = key_cols(kt0, sq.Lk, pad, w);
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
-      acc[f] = float4v{0, 0, 0, 0};
-      accp[f] = float4v{0, 0, 0, 0};
-#pragma unroll
-      for (int kk = 0; kk < D; kk += 32) {
-        acc[f] = mfma_bf16(frag_load(qs, strip, kk, lane, RS),
-                           frag_load(ks, f * 16, kk, lane, RS), acc[f]);
-        accp[f] = mfma_bf16(frag_load(dos, strip, kk, lane, RS),
-                            frag_load(vs, f * 16, kk, lane, RS), accp[f]);
-      }
-    }
-
-    // ---- scale*dS rows of this wave's strip
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float pv, dsv;
-        GQA_P_DS(f, r, pv, dsv);
-        (void)pv;
-        tile_store(dsn, strip + row_grp + r, f * 16 + col_base,
-                   bf16_bits(dsv));
-      }
+      float p[4], ds[4];
+      gqa_p_ds(f, acc, accp, kc, visible, st, scale, p, ds);
+      strip_stash(dsn, f, ds, w);
     }
     __builtin_amdgcn_wave_barrier();
-
-    // ---- dQ += (scale*dS) K_t
-#pragma unroll
-    for (int f = 0; f < D / 16; ++f) {
-#pragma unroll
-      for (int kk = 0; kk < TILE; kk += 32) {
-        accq[f] = mfma_bf16(frag_load(dsn, strip, kk, lane),
-                            frag_load(kt, f * 16, kk, lane), accq[f]);
-      }
-    }
+    strip_mma<TILE, D / 16, 128, 128>(accq, dsn, kt, w);
     __builtin_amdgcn_wave_barrier();
   }
 
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    int i = q0 + strip + row_grp + r;
-    if (i >= Lq) continue;
-    int64_t ob = ((tok0 + i) * Hq + h) * D;
-#pragma unroll
-    for (int f = 0; f < D / 16; ++f) {
-      dq[ob + f * 16 + col_base] = __float2bfloat16(accq[f][r]);
-    }
-  }
+  strip_store<D>(dq, sq.tok0(sq.Lq), Hq, h, q0, sq.Lq, accq, w);
 }
-
-#undef GQA_P_DS
 
 // ------------------------------------------------------------------ hosts
-
-bool gqa_ok_strides(const torch::Tensor& t) {
-  return t.stride(3) == 1 && t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0 &&
-         t.stride(2) % 8 == 0 &&
-         reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
-}
 
 struct GqaShape {
   int B, Hq, Hkv, Lq, Lk, D;
@@ -641,28 +437,10 @@ void gqa_allow_lds(K kernel, size_t smem, bool* done) {
 
 constexpr int kMaxDev = 64;
 
-// batch / head / row strides of one operand as the kernels take them
-struct GqaStrides {
-  int64_t b, h, l;
-};
-// [B,H,L,D] view
-GqaStrides gqa_bhld(const torch::Tensor& t) {
-  return {t.stride(0), t.stride(1), t.stride(2)};
-}
-// [B,L,H,D] view (dout)
-GqaStrides gqa_blhd(const torch::Tensor& t) {
-  return {t.stride(0), t.stride(2), t.stride(1)};
-}
-// token-major [T,H,D] view of packed sequences: no batch stride
-GqaStrides gqa_thd(const torch::Tensor& t) {
-  return {0, t.stride(1), t.stride(0)};
-}
-
-const __hip_bfloat16* gqa_cptr(const torch::Tensor& t) {
-  return reinterpret_cast<const __hip_bfloat16*>(t.data_ptr());
-}
-__hip_bfloat16* gqa_ptr(torch::Tensor& t) {
-  return reinterpret_cast<__hip_bfloat16*>(t.data_ptr());
+// q/k/v as the kernels take them: [B,H,L,D], or packed [T,H,D] when VARLEN
+template <bool VARLEN>
+FlashView gqa_view(const torch::Tensor& t) {
+  return VARLEN ? view_thd(t) : view_bhld(t);
 }
 
 // s.B counts sequences and s.Lq = s.Lk = max_seqlen when VARLEN; cu/T are
@@ -678,14 +456,11 @@ void gqa_launch_fwd(const GqaShape& s, const torch::Tensor& q,
   static bool done[kMaxDev] = {};
   gqa_allow_lds(gqa_fwd_kernel<D, VARLEN>, smem,
                 &done[q.get_device() % kMaxDev]);
-  const GqaStrides qs = VARLEN ? gqa_thd(q) : gqa_bhld(q),
-                   ks = VARLEN ? gqa_thd(k) : gqa_bhld(k),
-                   vs = VARLEN ? gqa_thd(v) : gqa_bhld(v);
   auto stream = at::cuda::getCurrentHIPStream();
   hipLaunchKernelGGL((gqa_fwd_kernel<D, VARLEN>), grid, dim3(256), smem,
-      stream, gqa_cptr(q), gqa_cptr(k), gqa_cptr(v), kp, gqa_ptr(out),
-      lse.data_ptr<float>(), s.Hq, s.Hkv, s.Lq, s.Lk, scale, causal,
-      qs.b, qs.h, qs.l, ks.b, ks.h, ks.l, vs.b, vs.h, vs.l, cu, T);
+      stream, gqa_view<VARLEN>(q), gqa_view<VARLEN>(k), gqa_view<VARLEN>(v),
+      kp, bf16_ptr(out), lse.data_ptr<float>(), s.Hq, s.Hkv, s.Lq, s.Lk,
+      scale, causal, cu, T);
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
@@ -699,14 +474,10 @@ void gqa_launch_bwd(const GqaShape& s, const torch::Tensor& dout,
                     bool causal, const int* cu = nullptr, int T = 0) {
   auto stream = at::cuda::getCurrentHIPStream();
   const int dev = q.get_device() % kMaxDev;
-  const __hip_bfloat16* dop = gqa_cptr(dout);
-  const __hip_bfloat16* qp = gqa_cptr(q);
-  const __hip_bfloat16* kp16 = gqa_cptr(k);
-  const __hip_bfloat16* vp = gqa_cptr(v);
-  const GqaStrides ds = VARLEN ? gqa_thd(dout) : gqa_blhd(dout),
-                   qs = VARLEN ? gqa_thd(q) : gqa_bhld(q),
-                   ks = VARLEN ? gqa_thd(k) : gqa_bhld(k),
-                   vs = VARLEN ? gqa_thd(v) : gqa_bhld(v);
+  // dout arrives as [B,Lq,Hq,D] | [T,Hq,D]
+  const FlashView dov = VARLEN ? view_thd(dout) : view_blhd(dout),
+                  qv = gqa_view<VARLEN>(q), kv = gqa_view<VARLEN>(k),
+                  vv = gqa_view<VARLEN>(v);
   {
     // packed sequences: the [T,Hq,D] rows are one batch item of T rows
     // (delta is per row, so sequence boundaries do not matter to it)
@@ -714,9 +485,8 @@ void gqa_launch_bwd(const GqaShape& s, const torch::Tensor& dout,
     const int dl_L = VARLEN ? T : s.Lq;
     int64_t n_rows = (int64_t)(VARLEN ? 1 : s.B) * s.Hq * dl_L;
     dim3 grid((unsigned int)((n_rows + rows_per_block - 1) / rows_per_block));
-    hipLaunchKernelGGL(gqa_delta_kernel<D>, grid, dim3(256), 0, stream, dop,
-        gqa_cptr(out), delta.data_ptr<float>(), s.Hq, dl_L, n_rows, ds.b,
-        ds.h, ds.l);
+    hipLaunchKernelGGL(gqa_delta_kernel<D>, grid, dim3(256), 0, stream, dov,
+        bf16_cptr(out), delta.data_ptr<float>(), s.Hq, dl_L, n_rows);
     C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   {
@@ -725,10 +495,9 @@ void gqa_launch_bwd(const GqaShape& s, const torch::Tensor& dout,
     static bool done[kMaxDev] = {};
     gqa_allow_lds(gqa_bwd_dkdv_kernel<D, VARLEN>, smem, &done[dev]);
     hipLaunchKernelGGL((gqa_bwd_dkdv_kernel<D, VARLEN>), grid, dim3(256),
-        smem, stream, dop, qp, kp16, vp, lse.data_ptr<float>(),
-        delta.data_ptr<float>(), kp, gqa_ptr(dk), gqa_ptr(dv),
-        s.Hq, s.Hkv, s.Lq, s.Lk, scale, causal, ds.b, ds.h, ds.l,
-        qs.b, qs.h, qs.l, ks.b, ks.h, ks.l, vs.b, vs.h, vs.l, cu, T);
+        smem, stream, dov, qv, kv, vv, lse.data_ptr<float>(),
+        delta.data_ptr<float>(), kp, bf16_ptr(dk), bf16_ptr(dv),
+        s.Hq, s.Hkv, s.Lq, s.Lk, scale, causal, cu, T);
     C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   {
@@ -737,20 +506,14 @@ void gqa_launch_bwd(const GqaShape& s, const torch::Tensor& dout,
     static bool done[kMaxDev] = {};
     gqa_allow_lds(gqa_bwd_dq_kernel<D, VARLEN>, smem, &done[dev]);
     hipLaunchKernelGGL((gqa_bwd_dq_kernel<D, VARLEN>), grid, dim3(256), smem,
-        stream, dop, qp, kp16, vp, lse.data_ptr<float>(),
-        delta.data_ptr<float>(), kp, gqa_ptr(dq),
-        s.Hq, s.Hkv, s.Lq, s.Lk, scale, causal, ds.b, ds.h, ds.l,
-        qs.b, qs.h, qs.l, ks.b, ks.h, ks.l, vs.b, vs.h, vs.l, cu, T);
+        stream, dov, qv, kv, vv, lse.data_ptr<float>(),
+        delta.data_ptr<float>(), kp, bf16_ptr(dq),
+        s.Hq, s.Hkv, s.Lq, s.Lk, scale, causal, cu, T);
     C10_HIP_KERNEL_LAUNCH_CHECK();
   }
 }
 
 // ---- packed sequences
-
-bool gqa_ok_strides_thd(const torch::Tensor& t) {
-  return t.stride(2) == 1 && t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0 &&
-         reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
-}
 
 // s.B = number of sequences, s.Lq = s.Lk = max_seqlen; returns T
 int gqa_varlen_check(const torch::Tensor& q, const torch::Tensor& k,
@@ -793,23 +556,18 @@ std::vector<torch::Tensor> gqa_attn_fwd(
     torch::Tensor q, torch::Tensor k, torch::Tensor v,
     c10::optional<torch::Tensor> key_pad, double scale, bool causal) {
   GqaShape s = gqa_check(q, k, v, key_pad);
-  torch::Tensor qn = gqa_ok_strides(q) ? q : q.contiguous();
-  torch::Tensor kn = gqa_ok_strides(k) ? k : k.contiguous();
-  torch::Tensor vn = gqa_ok_strides(v) ? v : v.contiguous();
+  // [B,H,L,D]: batch, head and row strides
+  torch::Tensor qn = kernel_readable(q, 3), kn = kernel_readable(k, 3),
+                vn = kernel_readable(v, 3);
   torch::Tensor kpc;
-  const bool* kp = nullptr;
-  if (key_pad.has_value()) {
-    kpc = key_pad->contiguous();
-    kp = kpc.data_ptr<bool>();
-  }
+  const bool* kp = pad_ptr(key_pad, kpc);
   auto out = torch::empty({s.B, s.Lq, s.Hq, s.D}, q.options());
   auto lse = torch::empty({s.B, s.Hq, s.Lq},
                           q.options().dtype(torch::kFloat32));
-  if (s.D == 64) {
-    gqa_launch_fwd<64, false>(s, qn, kn, vn, kp, out, lse, (float)scale, causal);
-  } else {
-    gqa_launch_fwd<128, false>(s, qn, kn, vn, kp, out, lse, (float)scale, causal);
-  }
+  dispatch_head_dim(s.D, [&](auto d) {
+    gqa_launch_fwd<decltype(d)::value, false>(s, qn, kn, vn, kp, out, lse,
+                                              (float)scale, causal);
+  });
   return {out, lse};
 }
 
@@ -830,29 +588,21 @@ std::vector<torch::Tensor> gqa_attn_bwd(
                   lse.dim() == 3 && lse.size(0) == s.B &&
                   lse.size(1) == s.Hq && lse.size(2) == s.Lq,
               "gqa_attn_bwd: lse must be the fp32 [B,Hq,Lq] forward lse");
-  torch::Tensor don = gqa_ok_strides(dout) ? dout : dout.contiguous();
-  torch::Tensor qn = gqa_ok_strides(q) ? q : q.contiguous();
-  torch::Tensor kn = gqa_ok_strides(k) ? k : k.contiguous();
-  torch::Tensor vn = gqa_ok_strides(v) ? v : v.contiguous();
+  torch::Tensor don = kernel_readable(dout, 3), qn = kernel_readable(q, 3),
+                kn = kernel_readable(k, 3), vn = kernel_readable(v, 3);
   torch::Tensor kpc;
-  const bool* kp = nullptr;
-  if (key_pad.has_value()) {
-    kpc = key_pad->contiguous();
-    kp = kpc.data_ptr<bool>();
-  }
+  const bool* kp = pad_ptr(key_pad, kpc);
   auto delta = torch::empty({s.B, s.Hq, s.Lq}, lse.options());
   // [B,L,H,D] storage, handed back as [B,H,L,D] views: the grads of the
   // q/k/v projections' .view().transpose(1,2) are then contiguous
   auto dq = torch::empty({s.B, s.Lq, s.Hq, s.D}, q.options());
   auto dk = torch::empty({s.B, s.Lk, s.Hkv, s.D}, k.options());
   auto dv = torch::empty({s.B, s.Lk, s.Hkv, s.D}, v.options());
-  if (s.D == 64) {
-    gqa_launch_bwd<64, false>(s, don, qn, kn, vn, out, lse, kp, delta, dq, dk, dv,
-                       (float)scale, causal);
-  } else {
-    gqa_launch_bwd<128, false>(s, don, qn, kn, vn, out, lse, kp, delta, dq, dk, dv,
-                        (float)scale, causal);
-  }
+  dispatch_head_dim(s.D, [&](auto d) {
+    gqa_launch_bwd<decltype(d)::value, false>(s, don, qn, kn, vn, out, lse,
+                                              kp, delta, dq, dk, dv,
+                                              (float)scale, causal);
+  });
   return {dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2)};
 }
 
@@ -861,21 +611,18 @@ std::vector<torch::Tensor> gqa_varlen_fwd(
     torch::Tensor cu_seqlens, int64_t max_seqlen, double scale) {
   GqaShape s;
   const int T = gqa_varlen_check(q, k, v, cu_seqlens, max_seqlen, &s);
-  torch::Tensor qn = gqa_ok_strides_thd(q) ? q : q.contiguous();
-  torch::Tensor kn = gqa_ok_strides_thd(k) ? k : k.contiguous();
-  torch::Tensor vn = gqa_ok_strides_thd(v) ? v : v.contiguous();
+  // [T,H,D]: token and head strides
+  torch::Tensor qn = kernel_readable(q, 2), kn = kernel_readable(k, 2),
+                vn = kernel_readable(v, 2);
   // zeros: tokens of no sequence (beyond cu[S]) are never written
   auto out = torch::zeros({T, s.Hq, s.D}, q.options());
   auto lse = torch::zeros({s.Hq, T}, q.options().dtype(torch::kFloat32));
   if (T == 0 || s.B == 0 || max_seqlen == 0) return {out, lse};
   const int* cu = cu_seqlens.data_ptr<int>();
-  if (s.D == 64) {
-    gqa_launch_fwd<64, true>(s, qn, kn, vn, nullptr, out, lse, (float)scale,
-                             true, cu, T);
-  } else {
-    gqa_launch_fwd<128, true>(s, qn, kn, vn, nullptr, out, lse, (float)scale,
-                              true, cu, T);
-  }
+  dispatch_head_dim(s.D, [&](auto d) {
+    gqa_launch_fwd<decltype(d)::value, true>(s, qn, kn, vn, nullptr, out, lse,
+                                             (float)scale, true, cu, T);
+  });
   return {out, lse};
 }
 
@@ -895,23 +642,19 @@ std::vector<torch::Tensor> gqa_varlen_bwd(
   TORCH_CHECK(lse.scalar_type() == torch::kFloat32 && lse.is_contiguous() &&
                   lse.dim() == 2 && lse.size(0) == s.Hq && lse.size(1) == T,
               "gqa_varlen_bwd: lse must be the fp32 [Hq,T] forward lse");
-  torch::Tensor don = gqa_ok_strides_thd(dout) ? dout : dout.contiguous();
-  torch::Tensor qn = gqa_ok_strides_thd(q) ? q : q.contiguous();
-  torch::Tensor kn = gqa_ok_strides_thd(k) ? k : k.contiguous();
-  torch::Tensor vn = gqa_ok_strides_thd(v) ? v : v.contiguous();
+  torch::Tensor don = kernel_readable(dout, 2), qn = kernel_readable(q, 2),
+                kn = kernel_readable(k, 2), vn = kernel_readable(v, 2);
   auto dq = torch::zeros({T, s.Hq, s.D}, q.options());
   auto dk = torch::zeros({T, s.Hkv, s.D}, k.options());
   auto dv = torch::zeros({T, s.Hkv, s.D}, v.options());
   if (T == 0 || s.B == 0 || max_seqlen == 0) return {dq, dk, dv};
   auto delta = torch::empty({s.Hq, T}, lse.options());
   const int* cu = cu_seqlens.data_ptr<int>();
-  if (s.D == 64) {
-    gqa_launch_bwd<64, true>(s, don, qn, kn, vn, out, lse, nullptr, delta, dq,
-                             dk, dv, (float)scale, true, cu, T);
-  } else {
-    gqa_launch_bwd<128, true>(s, don, qn, kn, vn, out, lse, nullptr, delta,
-                              dq, dk, dv, (float)scale, true, cu, T);
-  }
+  dispatch_head_dim(s.D, [&](auto d) {
+    gqa_launch_bwd<decltype(d)::value, true>(s, don, qn, kn, vn, out, lse,
+                                             nullptr, delta, dq, dk, dv,
+                                             (float)scale, true, cu, T);
+  });
   return {dq, dk, dv};
 }
 
