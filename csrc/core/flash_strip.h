@@ -1,14 +1,18 @@
 // Strip-level steps of a flash-attention tile, one level above mfma_tile.h
-// (attention_gqa, attention_beam).
+// (attention_gqa, attention_beam, attention_flash, hstu_attn).
 //
 // A block of four waves works on 64-row tiles; a wave owns a strip of 16
 // tile rows and holds, per 16-column fragment f, the C fragment
 // acc[f][r] = element (row + r, f*16 + col) of its strip (Strip below).
 // What a wave does with its strip is written here once: the strip x tile
 // MFMA products, the key-validity columns of a K tile, exact (-inf)
-// masking, the guarded running softmax, the P stash and the row store of a
-// finished strip. The head dim D and every row stride are compile-time;
-// staging, barriers and what a kernel iterates over stay with the kernel.
+// masking, the guarded running softmax, the P stash, the row store of a
+// finished strip, and the stashes and products of a backward tile. The head
+// dim D and every row stride are compile-time for attention_gqa and
+// attention_beam; attention_flash and hstu_attn take D (32 or 64) as a
+// kernel argument and use the runtime forms, all on [4] accumulators and
+// 128-byte rows. Staging, barriers and what a kernel iterates over stay
+// with the kernel.
 //
 // Bit-stability: every accumulator here is summed in one fixed order (f
 // outer, kk inner; the reductions as written), so two kernels that call
@@ -24,6 +28,10 @@ namespace genrec {
 struct FlashView {
   const __hip_bfloat16* p;
   int64_t b, h, l;
+  // row 0 of batch item bi, head hi
+  __device__ __forceinline__ const __hip_bfloat16* rows(int bi, int hi) const {
+    return p + (int64_t)bi * b + (int64_t)hi * h;
+  }
 };
 
 // Where a lane sits in its wave's strip.
@@ -54,6 +62,21 @@ __device__ __forceinline__ void strip_mma(float4v (&acc)[NF], const char* a,
   }
 }
 
+// Runtime form: K extent and live fragment count nf = (D + 15) / 16 as
+// arguments, 128-byte rows.
+__device__ __forceinline__ void strip_mma(float4v (&acc)[4], const char* a,
+                                          const char* b, int K, int nf,
+                                          const Strip& w) {
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    if (f >= nf) break;
+    for (int kk = 0; kk < K; kk += 32) {
+      acc[f] = mfma_bf16(frag_load(a, w.row0, kk, w.lane),
+                         frag_load(b, f * 16, kk, w.lane), acc[f]);
+    }
+  }
+}
+
 // Two strip products with the two MFMAs of one (f, kk) step issued back to
 // back, so each hides the other's operand loads. Per accumulator the
 // summation order is strip_mma's.
@@ -70,6 +93,24 @@ __device__ __forceinline__ void strip_mma2(float4v (&acc1)[NF], const char* a1,
                           frag_load(b1, f * 16, kk, w.lane, RS), acc1[f]);
       acc2[f] = mfma_bf16(frag_load(a2, w.row0, kk, w.lane, RS),
                           frag_load(b2, f * 16, kk, w.lane, RS), acc2[f]);
+    }
+  }
+}
+
+// Runtime form, as strip_mma's.
+__device__ __forceinline__ void strip_mma2(float4v (&acc1)[4], const char* a1,
+                                           const char* b1,
+                                           float4v (&acc2)[4], const char* a2,
+                                           const char* b2, int K, int nf,
+                                           const Strip& w) {
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    if (f >= nf) break;
+    for (int kk = 0; kk < K; kk += 32) {
+      acc1[f] = mfma_bf16(frag_load(a1, w.row0, kk, w.lane),
+                          frag_load(b1, f * 16, kk, w.lane), acc1[f]);
+      acc2[f] = mfma_bf16(frag_load(a2, w.row0, kk, w.lane),
+                          frag_load(b2, f * 16, kk, w.lane), acc2[f]);
     }
   }
 }
@@ -185,6 +226,43 @@ __device__ __forceinline__ void strip_stash(char* tile, int f,
   }
 }
 
+// The backward stashes take the fragment as packed bf16 bits, which an
+// epilogue converts element by element (four floats held across its
+// branches cost registers). Row-major as above, and transposed: the lane's
+// four values are consecutive columns row..row+3 of tile row f*16 + col,
+// one 8-byte store. Other waves read the transposed tile, behind a block
+// barrier.
+__device__ __forceinline__ void strip_stash(char* tile, int f, short4v x,
+                                            const Strip& w) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    tile_store(tile, w.row + r, f * 16 + w.col, (short)x[r]);
+  }
+}
+__device__ __forceinline__ void strip_stash_tr(char* tile, int f, short4v x,
+                                               const Strip& w) {
+  tile_store(tile, f * 16 + w.col, w.row, x);
+}
+
+// Product tail of a backward tile once the epilogue has stashed dS into dsn
+// (row-major) and dst (transposed) and A into adt (transposed):
+// dQ strip = dS K from the wave's own dsn rows and the staged kt = K^T, handed
+// to dq_done (atomics or a store); then, behind the block barrier that
+// completes dst / adt, dK += dS^T Q and dV += A^T dO, paired, from the
+// staged qt = Q^T and dot = dO^T.
+template <typename DqDone>
+__device__ __forceinline__ void strip_bwd_products(
+    const char* dsn, const char* kt, const char* dst, const char* qt,
+    const char* adt, const char* dot, int nf, float4v (&acck)[4],
+    float4v (&accv)[4], const Strip& w, DqDone&& dq_done) {
+  __builtin_amdgcn_wave_barrier();
+  float4v accq[4] = {};
+  strip_mma(accq, dsn, kt, TILE, nf, w);
+  dq_done(accq);
+  __syncthreads();
+  strip_mma2(acck, dst, qt, accv, adt, dot, TILE, nf, w);
+}
+
 // The K tile at kt0 of a flash forward for the wave's strip: S = Q K_t^T
 // from the staged qs [64][D] and ks [64][D], exact masking (keys at or
 // beyond Lk, pad keys, and what visible hides), the running-softmax step,
@@ -234,6 +312,25 @@ __device__ __forceinline__ void strip_store(__hip_bfloat16* __restrict__ dst,
     for (int f = 0; f < D / 16; ++f) {
       const float x = mul ? acc[f][r] * mul[r] : acc[f][r];
       dst[ob + f * 16 + w.col] = __float2bfloat16(x);
+    }
+  }
+}
+
+// Runtime form: the live rows of a strip into a contiguous [B,H,L,D] tensor
+// (bh = b * H + h), columns below D of acc[4].
+__device__ __forceinline__ void strip_store(__hip_bfloat16* __restrict__ dst,
+                                            int bh, int i0, int L, int D,
+                                            const float4v (&acc)[4],
+                                            const Strip& w) {
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    const int d = f * 16 + w.col;
+    if (d >= D) break;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = i0 + w.row + r;
+      if (i >= L) continue;
+      dst[((int64_t)bh * L + i) * D + d] = __float2bfloat16(acc[f][r]);
     }
   }
 }

@@ -1,9 +1,9 @@
 // Tile primitives shared by the v_mfma_f32_16x16x32_bf16 kernels
 // (attention_mfma, attention_flash, hstu_attn, attention_gqa, attention_beam,
 // skinny_gemm). This header stops at fragment level; the strip-level steps
-// of a flash tile that attention_gqa and attention_beam share (strip
-// products, key columns, masking, running softmax, P stash, row store) are
-// built on it in flash_strip.h.
+// of a flash tile that attention_gqa, attention_beam, attention_flash and
+// hstu_attn share (strip products, key columns, masking, running softmax,
+// stashes, row store, backward products) are built on it in flash_strip.h.
 //
 // LDS image: a tile is 64 rows of bf16 with 128-byte rows (64 columns) or
 // 256-byte rows (128 columns), stored with an XOR swizzle on 16-byte slots
@@ -131,6 +131,16 @@ __device__ __forceinline__ void xpose8x8(short (&vals)[8], int g) {
 
 // ---- per-chunk staging (one 8-element chunk per call; the caller owns the
 // loop, so several tensors' global loads stay in flight together)
+
+// chunk idx of a [64][64] tile walked row by row in 8-column chunks (the
+// loop of a kernel whose D <= 64 is an argument; a chunk at d0 >= D is zero)
+struct TileChunk {
+  int row, d0;
+};
+__device__ __forceinline__ TileChunk tile_chunk(int idx) {
+  return {idx / (TILE / 8), (idx % (TILE / 8)) * 8};
+}
+constexpr int TILE_CHUNKS = TILE * (TILE / 8);
 
 // 16-byte global load of the 8 bf16 at base[off..off+7]; zero when !pred
 // (the address is then neither formed nor read)

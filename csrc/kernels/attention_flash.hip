@@ -6,6 +6,8 @@
 // atomics. The tile math (running m/l rescale; single-pass backward via
 // the identity dot_i = rowsum(dO * O)) is validated at fragment
 // granularity against autograd in tools/sim_flash_tiles.py (~1e-15).
+// The strip steps (products, stashes, row stores, the backward's product
+// tail) are flash_strip.h's runtime forms: D is a kernel argument here.
 //
 // DEFAULT for Lk>64 since round 2 (GPU-validated; routes the COBRA
 // decoder). Stride-aware on the input side: q/k/v (+dout in backward)
@@ -17,15 +19,13 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
-#include "../core/mfma_tile.h"
+#include "../core/attn_host.h"
 
 namespace genrec {
 
 __global__ void __launch_bounds__(256)
 attn_fwd_flash_kernel(
-    const __hip_bfloat16* __restrict__ q,   // [B,H,Lq,D] contiguous
-    const __hip_bfloat16* __restrict__ k,   // [B,H,Lk,D]
-    const __hip_bfloat16* __restrict__ v,   // [B,H,Lk,D]
+    FlashView q, FlashView k, FlashView v,  // [B,H,L,D] views
     const void* __restrict__ bias,          // null | [H,Lq,Lk] | [B,H,Lq,Lk]
     const bool* __restrict__ key_pad,       // null | [B,Lk]
     const float* __restrict__ add_mask,     // null | [Lq,Lk]
@@ -37,16 +37,16 @@ attn_fwd_flash_kernel(
     const unsigned int* __restrict__ seed_dev,
     int B, int H, int Lq, int Lk, int D,
     float scale, int bias_dim, bool bias_bf16, bool causal,
-    float dropout_p, unsigned int seed,
-    int64_t q_sb, int64_t q_sh, int64_t q_sl,
-    int64_t k_sb, int64_t k_sh, int64_t k_sl,
-    int64_t v_sb, int64_t v_sh, int64_t v_sl) {
+    float dropout_p, unsigned int seed) {
   if (seed_dev) seed += *seed_dev;
   const float* bias_f = reinterpret_cast<const float*>(bias);
   const __hip_bfloat16* bias_b = reinterpret_cast<const __hip_bfloat16*>(bias);
   const int bh = blockIdx.x;
   const int b = bh / H, h = bh % H;
   const int q0 = blockIdx.y * TILE;
+  const __hip_bfloat16* qr = q.rows(b, h);
+  const __hip_bfloat16* kr = k.rows(b, h);
+  const __hip_bfloat16* vr = v.rows(b, h);
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* qs = smem;                 // [64][128B] Q rows
@@ -55,62 +55,52 @@ attn_fwd_flash_kernel(
   char* ps = vt + TILE * 128;      // [64][128B] P (per tile)
 
   const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int col_base = frag_col(lane);
-  const int row_grp = frag_row0(lane);
-  const int strip = wid * 16;
+  const Strip w(tid);
   const float inv_keep = dropout_p > 0.f ? 1.0f / (1.0f - dropout_p) : 1.0f;
 
   // ---- stage Q once
-  for (int idx = tid; idx < TILE * (TILE / 8); idx += blockDim.x) {
-    int row = idx / (TILE / 8);
-    int d0 = (idx % (TILE / 8)) * 8;
-    int qi = q0 + row;
-    tile_store(qs, row, d0,
-               load8(q, (int64_t)b * q_sb + h * q_sh + qi * q_sl + d0,
-                     qi < Lq && d0 < D));
+  for (int idx = tid; idx < TILE_CHUNKS; idx += blockDim.x) {
+    const TileChunk c = tile_chunk(idx);
+    const int qi = q0 + c.row;
+    tile_store(qs, c.row, c.d0,
+               load8(qr, qi * q.l + c.d0, qi < Lq && c.d0 < D));
   }
 
+  // Running softmax state. Not flash_strip.h's RunningSoftmax: a row whose
+  // every score is -inf (an additive mask can do that) saves m = -1e30 here
+  // and would save -inf there; every other stored bit is the same.
   float m_row[4] = {-1e30f, -1e30f, -1e30f, -1e30f};
   float l_row[4] = {0.f, 0.f, 0.f, 0.f};
-  float4v accO[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+  float4v accO[4] = {};
   const int nfrag_d = (D + 15) / 16;
 
   for (int kt0 = 0; kt0 < Lk; kt0 += TILE) {
     __syncthreads();  // previous iteration's ps/ks/vt fully consumed
     // ---- stage K tile + V^T tile
-    for (int idx = tid; idx < TILE * (TILE / 8); idx += blockDim.x) {
-      int row = idx / (TILE / 8);
-      int d0 = (idx % (TILE / 8)) * 8;
-      int kj = kt0 + row;
-      const bool ok = kj < Lk && d0 < D;
-      tile_store(ks, row, d0,
-                 load8(k, (int64_t)b * k_sb + h * k_sh + kj * k_sl + d0, ok));
-      tile_store_tr(
-          vt, row, d0, lane,
-          load8(v, (int64_t)b * v_sb + h * v_sh + kj * v_sl + d0, ok));
+    for (int idx = tid; idx < TILE_CHUNKS; idx += blockDim.x) {
+      const TileChunk c = tile_chunk(idx);
+      const int kj = kt0 + c.row;
+      const bool ok = kj < Lk && c.d0 < D;
+      tile_store(ks, c.row, c.d0, load8(kr, kj * k.l + c.d0, ok));
+      tile_store_tr(vt, c.row, c.d0, w.lane,
+                    load8(vr, kj * v.l + c.d0, ok));
     }
     __syncthreads();
 
     // ---- S = Q K_t^T
-    float4v acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      for (int kk = 0; kk < D; kk += 32) {
-        acc[f] = mfma_bf16(frag_load(qs, strip, kk, lane),
-                           frag_load(ks, f * 16, kk, lane), acc[f]);
-      }
-    }
+    float4v acc[4] = {};
+    strip_mma(acc, qs, ks, D, 4, w);
 
-    // ---- epilogue: masks + running softmax state
+    // ---- epilogue: masks. The kernel's own masks score NEG_BIG, which
+    // stays in the softmax; -inf (outside the tensors, or from add_mask)
+    // has probability exactly 0.
     float s_val[4][4];
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        int i = q0 + strip + row_grp + r;
-        int j = kt0 + f * 16 + col_base;
+        int i = q0 + w.row + r;
+        int j = kt0 + f * 16 + w.col;
         float s = acc[f][r];
         if (i < Lq && j < Lk) {
           s *= scale;
@@ -156,58 +146,41 @@ attn_fwd_flash_kernel(
     for (int f = 0; f < 4; ++f) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        int i = q0 + strip + row_grp + r;
-        int j = kt0 + f * 16 + col_base;
-        float p = s_val[f][r];
+        int i = q0 + w.row + r;
+        int j = kt0 + f * 16 + w.col;
         if (i < Lq && j < Lk && dropout_p > 0.f) {
           unsigned long long gidx = idx4(b, h, i, j, H, Lq, Lk);
           bool keep = (hash_rng(seed, gidx) & 0xFFFFFF) >=
                       (unsigned int)(dropout_p * 16777216.0f);
           drop_mask[gidx] = keep;
-          p = keep ? p * inv_keep : 0.f;
+          s_val[f][r] = keep ? s_val[f][r] * inv_keep : 0.f;
         }
-        tile_store(ps, strip + row_grp + r, j - kt0, bf16_bits(p));
       }
+      strip_stash(ps, f, s_val[f], w);
     }
     __builtin_amdgcn_wave_barrier();
 
     // ---- accO += P V_t
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      if (f >= nfrag_d) break;
-      for (int kk = 0; kk < TILE; kk += 32) {
-        accO[f] = mfma_bf16(frag_load(ps, strip, kk, lane),
-                            frag_load(vt, f * 16, kk, lane), accO[f]);
-      }
-    }
+    strip_mma(accO, ps, vt, TILE, nfrag_d, w);
   }
 
   // ---- finalize: normalize, query mask, write out + (m, l)
 #pragma unroll
-  for (int f = 0; f < 4; ++f) {
-    if (f >= nfrag_d) break;
+  for (int r = 0; r < 4; ++r) {
+    const int i = q0 + w.row + r;
+    if (i >= Lq) continue;
+    const float inv = (l_row[r] > 0.f) ? 1.0f / l_row[r] : 0.f;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int i = q0 + strip + row_grp + r;
-      int d = f * 16 + col_base;
-      if (i < Lq && d < D) {
-        float inv = (l_row[r] > 0.f) ? 1.0f / l_row[r] : 0.f;
-        float o = accO[f][r] * inv;
-        if (query_mask) o *= query_mask[(int64_t)b * Lq + i];
-        out[idx4(b, h, i, d, H, Lq, D)] = __float2bfloat16(o);
-      }
+    for (int f = 0; f < 4; ++f) {
+      accO[f][r] *= inv;
+      if (query_mask) accO[f][r] *= query_mask[(int64_t)b * Lq + i];
+    }
+    if (w.col == 0) {
+      ml_saved[((int64_t)bh * Lq + i) * 2 + 0] = m_row[r];
+      ml_saved[((int64_t)bh * Lq + i) * 2 + 1] = l_row[r];
     }
   }
-  if (col_base == 0) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int i = q0 + strip + row_grp + r;
-      if (i < Lq) {
-        ml_saved[((int64_t)bh * Lq + i) * 2 + 0] = m_row[r];
-        ml_saved[((int64_t)bh * Lq + i) * 2 + 1] = l_row[r];
-      }
-    }
-  }
+  strip_store(out, bh, q0, Lq, D, accO, w);
 }
 
 // Backward: one block per (b, h, k-tile); loops q-tiles. dK/dV accumulate
@@ -215,10 +188,7 @@ attn_fwd_flash_kernel(
 // atomicAdd (each (i,d) is touched by n_k_tiles blocks).
 __global__ void __launch_bounds__(256)
 attn_bwd_flash_kernel(
-    const __hip_bfloat16* __restrict__ dout,  // [B,H,Lq,D]
-    const __hip_bfloat16* __restrict__ q,
-    const __hip_bfloat16* __restrict__ k,
-    const __hip_bfloat16* __restrict__ v,
+    FlashView dout, FlashView q, FlashView k, FlashView v,  // [B,H,L,D] views
     const float* __restrict__ s_saved,        // [B,H,Lq,Lk]
     const float* __restrict__ ml_saved,       // [B,H,Lq,2]
     const float* __restrict__ dot_row,        // [B,H,Lq] rowsum(dO*O)
@@ -229,14 +199,14 @@ attn_bwd_flash_kernel(
     __hip_bfloat16* __restrict__ dv_out,
     float* __restrict__ ds_saved,             // null | [B,H,Lq,Lk]
     int B, int H, int Lq, int Lk, int D,
-    float scale, float dropout_p,
-    int64_t do_sb, int64_t do_sh, int64_t do_sl,
-    int64_t q_sb, int64_t q_sh, int64_t q_sl,
-    int64_t k_sb, int64_t k_sh, int64_t k_sl,
-    int64_t v_sb, int64_t v_sh, int64_t v_sl) {
+    float scale, float dropout_p) {
   const int bh = blockIdx.x;
   const int b = bh / H, h = bh % H;
   const int kt0 = blockIdx.y * TILE;
+  const __hip_bfloat16* dor = dout.rows(b, h);
+  const __hip_bfloat16* qr = q.rows(b, h);
+  const __hip_bfloat16* kr = k.rows(b, h);
+  const __hip_bfloat16* vr = v.rows(b, h);
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* vs = smem;                 // [64][128B] V_t rows (persistent)
@@ -249,68 +219,51 @@ attn_bwd_flash_kernel(
   char* adt = dst + TILE * 128;    // [64(j)][128B(i)] A_d^T
 
   const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int col_base = frag_col(lane);
-  const int row_grp = frag_row0(lane);
-  const int strip = wid * 16;
-  const int i0g = strip + row_grp;  // 8B-aligned store base (see mfma bwd)
+  const Strip w(tid);
   const float inv_keep = dropout_p > 0.f ? 1.0f / (1.0f - dropout_p) : 1.0f;
 
   // ---- stage V_t natural + K_t^T once
-  for (int idx = tid; idx < TILE * (TILE / 8); idx += blockDim.x) {
-    int row = idx / (TILE / 8);
-    int d0 = (idx % (TILE / 8)) * 8;
-    int kj = kt0 + row;
-    const bool ok = kj < Lk && d0 < D;
-    short8v vv8 = load8(
-        v, (int64_t)b * v_sb + h * v_sh + kj * v_sl + d0, ok);
-    short8v kk8 = load8(
-        k, (int64_t)b * k_sb + h * k_sh + kj * k_sl + d0, ok);
-    tile_store(vs, row, d0, vv8);
-    tile_store_tr(kt, row, d0, lane, kk8);
+  for (int idx = tid; idx < TILE_CHUNKS; idx += blockDim.x) {
+    const TileChunk c = tile_chunk(idx);
+    const int kj = kt0 + c.row;
+    const bool ok = kj < Lk && c.d0 < D;
+    short8v vv8 = load8(vr, kj * v.l + c.d0, ok);
+    short8v kk8 = load8(kr, kj * k.l + c.d0, ok);
+    tile_store(vs, c.row, c.d0, vv8);
+    tile_store_tr(kt, c.row, c.d0, w.lane, kk8);
   }
 
   const int nfrag_d = (D + 15) / 16;
-  float4v acck[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-  float4v accv[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+  float4v acck[4] = {};
+  float4v accv[4] = {};
 
   for (int q0 = 0; q0 < Lq; q0 += TILE) {
     __syncthreads();
     // ---- stage dO natural + dO^T + Q^T for this q-tile
-    for (int idx = tid; idx < TILE * (TILE / 8); idx += blockDim.x) {
-      int row = idx / (TILE / 8);
-      int d0 = (idx % (TILE / 8)) * 8;
-      int qi = q0 + row;
-      const bool ok = qi < Lq && d0 < D;
-      short8v dd8 = load8(
-          dout, (int64_t)b * do_sb + h * do_sh + qi * do_sl + d0, ok);
-      short8v qq8 = load8(
-          q, (int64_t)b * q_sb + h * q_sh + qi * q_sl + d0, ok);
-      tile_store(dos, row, d0, dd8);
-      tile_store_tr(dot, row, d0, lane, dd8);
-      tile_store_tr(qt, row, d0, lane, qq8);
+    for (int idx = tid; idx < TILE_CHUNKS; idx += blockDim.x) {
+      const TileChunk c = tile_chunk(idx);
+      const int qi = q0 + c.row;
+      const bool ok = qi < Lq && c.d0 < D;
+      short8v dd8 = load8(dor, qi * dout.l + c.d0, ok);
+      short8v qq8 = load8(qr, qi * q.l + c.d0, ok);
+      tile_store(dos, c.row, c.d0, dd8);
+      tile_store_tr(dot, c.row, c.d0, w.lane, dd8);
+      tile_store_tr(qt, c.row, c.d0, w.lane, qq8);
     }
     __syncthreads();
 
     // ---- dA = dO V_t^T : C rows = q rows (this wave's strip)
-    float4v acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      for (int kk = 0; kk < D; kk += 32) {
-        acc[f] = mfma_bf16(frag_load(dos, strip, kk, lane),
-                           frag_load(vs, f * 16, kk, lane), acc[f]);
-      }
-    }
+    float4v acc[4] = {};
+    strip_mma(acc, dos, vs, D, 4, w);
 
     // ---- epilogue: reconstruct P, dS = P (M*dA - dot_i); stash tiles
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
-      short4v dpack, apack;
+      short4v ds, ad;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        int i = q0 + strip + row_grp + r;
-        int j = kt0 + f * 16 + col_base;
+        int i = q0 + w.row + r;
+        int j = kt0 + f * 16 + w.col;
         float dval = 0.f, aval = 0.f;
         if (i < Lq && j < Lk) {
           float m = ml_saved[((int64_t)bh * Lq + i) * 2 + 0];
@@ -327,71 +280,37 @@ attn_bwd_flash_kernel(
           aval = p * mult;
           if (ds_saved) ds_saved[idx4(b, h, i, j, H, Lq, Lk)] = dval;
         }
-        dpack[r] = bf16_bits(dval * scale);
-        apack[r] = bf16_bits(aval);
-        tile_store(dsn, strip + row_grp + r, f * 16 + col_base, dpack[r]);
+        ds[r] = bf16_bits(dval * scale);
+        ad[r] = bf16_bits(aval);
       }
-      int jl = f * 16 + col_base;  // tile-local j row of the transposed tiles
-      tile_store(dst, jl, i0g, dpack);
-      tile_store(adt, jl, i0g, apack);
+      strip_stash(dsn, f, ds, w);
+      strip_stash_tr(dst, f, ds, w);
+      strip_stash_tr(adt, f, ad, w);
     }
-    // dQ uses only this wave's dS rows
-    __builtin_amdgcn_wave_barrier();
 
-    {  // dQ[strip rows of this q-tile] += (scale*dS) @ K_t  (atomic fp32)
-      float4v accq[4] = {{0, 0, 0, 0}, {0, 0, 0, 0},
-                         {0, 0, 0, 0}, {0, 0, 0, 0}};
+    // dQ rows of this q-tile += (scale*dS) K_t (atomic fp32), then
+    // dK_t += (scale*dS)^T Q ; dV_t += A_d^T dO (accumulate over q0)
+    strip_bwd_products(
+        dsn, kt, dst, qt, adt, dot, nfrag_d, acck, accv, w,
+        [&](const float4v (&accq)[4]) {
 #pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        if (f >= nfrag_d) break;
-        for (int kk = 0; kk < TILE; kk += 32) {
-          accq[f] = mfma_bf16(frag_load(dsn, strip, kk, lane),
-                              frag_load(kt, f * 16, kk, lane), accq[f]);
-        }
-      }
+          for (int f = 0; f < 4; ++f) {
+            if (f >= nfrag_d) break;
 #pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        if (f >= nfrag_d) break;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          int i = q0 + strip + row_grp + r;
-          int d = f * 16 + col_base;
-          if (i < Lq && d < D) {
-            atomicAdd(&dq_f32[idx4(b, h, i, d, H, Lq, D)], accq[f][r]);
+            for (int r = 0; r < 4; ++r) {
+              int i = q0 + w.row + r;
+              int d = f * 16 + w.col;
+              if (i < Lq && d < D) {
+                atomicAdd(&dq_f32[idx4(b, h, i, d, H, Lq, D)], accq[f][r]);
+              }
+            }
           }
-        }
-      }
-    }
-    __syncthreads();  // dst/adt complete across waves
-
-    {  // dK_t += (scale*dS)^T Q ; dV_t += A_d^T dO  (accumulate over q0)
-#pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        if (f >= nfrag_d) break;
-        for (int kk = 0; kk < TILE; kk += 32) {
-          acck[f] = mfma_bf16(frag_load(dst, strip, kk, lane),
-                              frag_load(qt, f * 16, kk, lane), acck[f]);
-          accv[f] = mfma_bf16(frag_load(adt, strip, kk, lane),
-                              frag_load(dot, f * 16, kk, lane), accv[f]);
-        }
-      }
-    }
+        });
   }
 
   // ---- write dK/dV rows of this k-tile
-#pragma unroll
-  for (int f = 0; f < 4; ++f) {
-    if (f >= nfrag_d) break;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int j = kt0 + strip + row_grp + r;
-      int d = f * 16 + col_base;
-      if (j < Lk && d < D) {
-        dk_out[idx4(b, h, j, d, H, Lk, D)] = __float2bfloat16(acck[f][r]);
-        dv_out[idx4(b, h, j, d, H, Lk, D)] = __float2bfloat16(accv[f][r]);
-      }
-    }
-  }
+  strip_store(dk_out, bh, kt0, Lk, D, acck, w);
+  strip_store(dv_out, bh, kt0, Lk, D, accv, w);
 }
 
 // ------------------------------------------------------------------ hosts
@@ -407,17 +326,12 @@ std::vector<torch::Tensor> attn_fwd_flash(
   const int B = q.size(0), H = q.size(1), Lq = q.size(2), D = q.size(3);
   const int Lk = k.size(2);
   TORCH_CHECK(D <= TILE && D % 32 == 0);
-  // stride-aware over [B,H,L,D] views (d must be innermost; 16-byte
-  // short8 loads need 8-element-aligned batch/head/row strides — true
-  // for every [B,L,H,D] transpose view at D % 32 == 0). Anything else
-  // is copied here, not in the op layer.
-  auto ok_strides = [](const torch::Tensor& t) {
-    return t.stride(3) == 1 && t.stride(0) % 8 == 0 &&
-           t.stride(1) % 8 == 0 && t.stride(2) % 8 == 0;
-  };
-  torch::Tensor qn = ok_strides(q) ? q : q.contiguous();
-  torch::Tensor kn = ok_strides(k) ? k : k.contiguous();
-  torch::Tensor vn = ok_strides(v) ? v : v.contiguous();
+  // stride-aware over [B,H,L,D] views (every [B,L,H,D] transpose view at
+  // D % 32 == 0 qualifies). Anything else is copied here, not in the op
+  // layer.
+  torch::Tensor qn = kernel_readable(q, 3);
+  torch::Tensor kn = kernel_readable(k, 3);
+  torch::Tensor vn = kernel_readable(v, 3);
   auto out = torch::empty({B, H, Lq, D}, q.options());
   auto opts_f = q.options().dtype(torch::kFloat32);
   auto s_saved = torch::empty({B, H, Lq, Lk}, opts_f);
@@ -428,7 +342,7 @@ std::vector<torch::Tensor> attn_fwd_flash(
   } else {
     dmask = torch::empty({0}, q.options().dtype(torch::kUInt8));
   }
-  torch::Tensor bias_c;
+  torch::Tensor bias_c, pad_c;
   int bias_dim = 0;
   bool bias_bf16 = false;
   if (bias.has_value()) {
@@ -445,24 +359,18 @@ std::vector<torch::Tensor> attn_fwd_flash(
   size_t smem = 4 * TILE * 128;
   auto stream = at::cuda::getCurrentHIPStream();
   hipLaunchKernelGGL(attn_fwd_flash_kernel, grid, block, smem, stream,
-      reinterpret_cast<const __hip_bfloat16*>(qn.data_ptr()),
-      reinterpret_cast<const __hip_bfloat16*>(kn.data_ptr()),
-      reinterpret_cast<const __hip_bfloat16*>(vn.data_ptr()),
+      view_bhld(qn), view_bhld(kn), view_bhld(vn),
       bias_dim ? bias_c.data_ptr() : nullptr,
-      key_pad.has_value() ? key_pad->data_ptr<bool>() : nullptr,
+      pad_ptr(key_pad, pad_c),
       add_mask.has_value() ? am_f.data_ptr<float>() : nullptr,
       query_mask.has_value() ? qm_f.data_ptr<float>() : nullptr,
-      reinterpret_cast<__hip_bfloat16*>(out.data_ptr()),
-      s_saved.data_ptr<float>(), ml.data_ptr<float>(),
+      bf16_ptr(out), s_saved.data_ptr<float>(), ml.data_ptr<float>(),
       dropout_p > 0 ? dmask.data_ptr<unsigned char>() : nullptr,
       seed_dev.has_value()
           ? reinterpret_cast<const unsigned int*>(seed_dev->data_ptr())
           : nullptr,
       B, H, Lq, Lk, D, (float)scale, bias_dim, bias_bf16, causal,
-      (float)dropout_p, (unsigned int)seed,
-      qn.stride(0), qn.stride(1), qn.stride(2),
-      kn.stride(0), kn.stride(1), kn.stride(2),
-      vn.stride(0), vn.stride(1), vn.stride(2));
+      (float)dropout_p, (unsigned int)seed);
   return {out, s_saved, ml, dmask};
 }
 
@@ -473,14 +381,10 @@ std::vector<torch::Tensor> attn_bwd_flash(
     double scale, double dropout_p, bool bias_grad, int64_t bias_dim) {
   const int B = q.size(0), H = q.size(1), Lq = q.size(2), D = q.size(3);
   const int Lk = k.size(2);
-  auto ok_strides = [](const torch::Tensor& t) {
-    return t.stride(3) == 1 && t.stride(0) % 8 == 0 &&
-           t.stride(1) % 8 == 0 && t.stride(2) % 8 == 0;
-  };
-  torch::Tensor don = ok_strides(dout) ? dout : dout.contiguous();
-  torch::Tensor qn = ok_strides(q) ? q : q.contiguous();
-  torch::Tensor kn = ok_strides(k) ? k : k.contiguous();
-  torch::Tensor vn = ok_strides(v) ? v : v.contiguous();
+  torch::Tensor don = kernel_readable(dout, 3);
+  torch::Tensor qn = kernel_readable(q, 3);
+  torch::Tensor kn = kernel_readable(k, 3);
+  torch::Tensor vn = kernel_readable(v, 3);
   // flash identity: dot_i = rowsum(dO * O) (tools/sim_flash_tiles.py)
   auto dot_row = (don.to(torch::kFloat32) * out.to(torch::kFloat32))
                      .sum(-1).contiguous();
@@ -503,22 +407,13 @@ std::vector<torch::Tensor> attn_bwd_flash(
   size_t smem = 8 * TILE * 128;
   auto stream = at::cuda::getCurrentHIPStream();
   hipLaunchKernelGGL(attn_bwd_flash_kernel, grid, block, smem, stream,
-      reinterpret_cast<const __hip_bfloat16*>(don.data_ptr()),
-      reinterpret_cast<const __hip_bfloat16*>(qn.data_ptr()),
-      reinterpret_cast<const __hip_bfloat16*>(kn.data_ptr()),
-      reinterpret_cast<const __hip_bfloat16*>(vn.data_ptr()),
+      view_bhld(don), view_bhld(qn), view_bhld(kn), view_bhld(vn),
       s_saved.data_ptr<float>(), ml.data_ptr<float>(),
       dot_row.data_ptr<float>(),
       query_mask.has_value() ? qm_f.data_ptr<float>() : nullptr,
       dropout_p > 0 ? drop_mask.data_ptr<unsigned char>() : nullptr,
-      dq_f32.data_ptr<float>(),
-      reinterpret_cast<__hip_bfloat16*>(dk.data_ptr()),
-      reinterpret_cast<__hip_bfloat16*>(dv.data_ptr()), ds_ptr,
-      B, H, Lq, Lk, D, (float)scale, (float)dropout_p,
-      don.stride(0), don.stride(1), don.stride(2),
-      qn.stride(0), qn.stride(1), qn.stride(2),
-      kn.stride(0), kn.stride(1), kn.stride(2),
-      vn.stride(0), vn.stride(1), vn.stride(2));
+      dq_f32.data_ptr<float>(), bf16_ptr(dk), bf16_ptr(dv), ds_ptr,
+      B, H, Lq, Lk, D, (float)scale, (float)dropout_p);
   auto dq = dq_f32.to(torch::kBFloat16);
   torch::Tensor dbias;
   if (bias_grad) {

@@ -13,11 +13,14 @@
 // are reduced per-block into LDS histograms (one head per block, <=
 // n_pos + n_time floats) and flushed with one global atomicAdd per bucket,
 // then dQ/dK/dV run as MFMA in the same launch.
+//
+// One 64-row tile per (b, h); the strip steps are flash_strip.h's runtime
+// forms (D is a kernel argument), shared with attention_flash.hip.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
-#include "../core/mfma_tile.h"
+#include "../core/attn_host.h"
 
 namespace genrec {
 
@@ -30,15 +33,14 @@ __device__ __forceinline__ int time_bucket(long long ti, long long tj,
   return min(max(b, 0), n_buckets - 1);
 }
 
-template <typename BT>
 __global__ void __launch_bounds__(256)
 hstu_attn_fwd_kernel(
     const __hip_bfloat16* __restrict__ q,     // [B,H,L,D]
     const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v,
     const int* __restrict__ pos_bucket,       // [L,L]
-    const BT* __restrict__ pos_table,         // [n_pos, H]
-    const BT* __restrict__ time_table,        // null | [n_time, H]
+    const __hip_bfloat16* __restrict__ pos_table,   // [n_pos, H]
+    const __hip_bfloat16* __restrict__ time_table,  // null | [n_time, H]
     const long long* __restrict__ ts,         // null | [B,L]
     const bool* __restrict__ key_pad,         // null | [B,L]
     __hip_bfloat16* __restrict__ out,
@@ -54,41 +56,31 @@ hstu_attn_fwd_kernel(
   char* ps = vt + TILE * 128;
 
   const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
+  const Strip w(tid);
 
-  for (int idx = tid; idx < TILE * (TILE / 8); idx += blockDim.x) {
-    int row = idx / (TILE / 8);
-    int d0 = (idx % (TILE / 8)) * 8;
-    const bool ok = row < L && d0 < D;
-    const int64_t src = idx4(b, h, row, d0, H, L, D);
-    tile_store(qs, row, d0, load8(q, src, ok));
-    tile_store(ks, row, d0, load8(k, src, ok));
+  for (int idx = tid; idx < TILE_CHUNKS; idx += blockDim.x) {
+    const TileChunk c = tile_chunk(idx);
+    const bool ok = c.row < L && c.d0 < D;
+    const int64_t src = idx4(b, h, c.row, c.d0, H, L, D);
+    tile_store(qs, c.row, c.d0, load8(q, src, ok));
+    tile_store(ks, c.row, c.d0, load8(k, src, ok));
     // V^T: coalesced natural-row load + in-register 8x8 transpose
-    tile_store_tr(vt, row, d0, lane, load8(v, src, ok));
+    tile_store_tr(vt, c.row, c.d0, w.lane, load8(v, src, ok));
   }
   __syncthreads();
 
-  const int strip = wid * 16;
-  float4v acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-#pragma unroll
-  for (int f = 0; f < 4; ++f) {
-    for (int kk = 0; kk < D; kk += 32) {
-      acc[f] = mfma_bf16(frag_load(qs, strip, kk, lane),
-                         frag_load(ks, f * 16, kk, lane), acc[f]);
-    }
-  }
+  float4v acc[4] = {};
+  strip_mma(acc, qs, ks, D, 4, w);
 
-  const int col_base = frag_col(lane);
-  const int row_grp = frag_row0(lane);
 #pragma unroll
   for (int f = 0; f < 4; ++f) {
+    short4v p;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      int i = strip + row_grp + r;
-      int j = f * 16 + col_base;
+      int i = w.row + r;
+      int j = f * 16 + w.col;
       float s = acc[f][r];
-      float p = 0.f;
+      float pv = 0.f;
       if (i < L && j < L) {
         s += to_f32(pos_table[(int64_t)pos_bucket[i * L + j] * H + h]);
         if (time_table) {
@@ -99,38 +91,19 @@ hstu_attn_fwd_kernel(
         if (j > i) s = NEG_BIG;                                     // causal
         if (key_pad && key_pad[(int64_t)b * L + j]) s = NEG_BIG;    // pad
         s_saved[idx4(b, h, i, j, H, L, L)] = s;
-        p = s * sigmoidf_dev(s);
+        pv = s * sigmoidf_dev(s);
       }
-      tile_store(ps, i, j, bf16_bits(p));
+      p[r] = bf16_bits(pv);
     }
+    strip_stash(ps, f, p, w);
   }
   __builtin_amdgcn_wave_barrier();
 
-  float4v acc2[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-  const int nfrag_d = (D + 15) / 16;
-#pragma unroll
-  for (int f = 0; f < 4; ++f) {
-    if (f >= nfrag_d) break;
-    for (int kk = 0; kk < TILE; kk += 32) {
-      acc2[f] = mfma_bf16(frag_load(ps, strip, kk, lane),
-                          frag_load(vt, f * 16, kk, lane), acc2[f]);
-    }
-  }
-#pragma unroll
-  for (int f = 0; f < 4; ++f) {
-    if (f >= nfrag_d) break;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int i = strip + row_grp + r;
-      int d = f * 16 + col_base;
-      if (i < L && d < D) {
-        out[idx4(b, h, i, d, H, L, D)] = __float2bfloat16(acc2[f][r]);
-      }
-    }
-  }
+  float4v acc2[4] = {};
+  strip_mma(acc2, ps, vt, TILE, (D + 15) / 16, w);
+  strip_store(out, bh, 0, L, D, acc2, w);
 }
 
-template <typename BT>
 __global__ void __launch_bounds__(256)
 hstu_attn_bwd_kernel(
     const __hip_bfloat16* __restrict__ dout,
@@ -161,52 +134,38 @@ hstu_attn_bwd_kernel(
   float* hist = reinterpret_cast<float*>(adt + TILE * 128);  // [n_pos+n_time]
 
   const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
+  const Strip w(tid);
   const int n_hist = n_pos + n_time;
   for (int i = tid; i < n_hist; i += blockDim.x) hist[i] = 0.f;
 
-  for (int idx = tid; idx < TILE * (TILE / 8); idx += blockDim.x) {
-    int row = idx / (TILE / 8);
-    int d0 = (idx % (TILE / 8)) * 8;
-    const bool ok = row < L && d0 < D;
-    const int64_t src = idx4(b, h, row, d0, H, L, D);
+  for (int idx = tid; idx < TILE_CHUNKS; idx += blockDim.x) {
+    const TileChunk c = tile_chunk(idx);
+    const bool ok = c.row < L && c.d0 < D;
+    const int64_t src = idx4(b, h, c.row, c.d0, H, L, D);
     short8v dd8 = load8(dout, src, ok);
     short8v vv8 = load8(v, src, ok);
     short8v kk8 = load8(k, src, ok);
     short8v qq8 = load8(q, src, ok);
-    tile_store(dos, row, d0, dd8);
-    tile_store(vs, row, d0, vv8);
+    tile_store(dos, c.row, c.d0, dd8);
+    tile_store(vs, c.row, c.d0, vv8);
     // K^T/Q^T/dO^T: coalesced natural-row b128 loads + in-register 8x8
     // transpose, one b128 LDS store per tensor
-    tile_store_tr(kt, row, d0, lane, kk8);
-    tile_store_tr(qt, row, d0, lane, qq8);
-    tile_store_tr(dot, row, d0, lane, dd8);
+    tile_store_tr(kt, c.row, c.d0, w.lane, kk8);
+    tile_store_tr(qt, c.row, c.d0, w.lane, qq8);
+    tile_store_tr(dot, c.row, c.d0, w.lane, dd8);
   }
   __syncthreads();
 
-  const int strip = wid * 16;
-  float4v acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-#pragma unroll
-  for (int f = 0; f < 4; ++f) {
-    for (int kk = 0; kk < D; kk += 32) {
-      acc[f] = mfma_bf16(frag_load(dos, strip, kk, lane),
-                         frag_load(vs, f * 16, kk, lane), acc[f]);
-    }
-  }
+  float4v acc[4] = {};
+  strip_mma(acc, dos, vs, D, 4, w);
 
-  const int col_base = frag_col(lane);
-  const int row_grp = frag_row0(lane);
-  // transposed-tile stores pack a lane's 4 r-values (consecutive columns
-  // of row j) into ONE aligned 8-byte ds_write — see attention_mfma.hip
-  const int i0 = strip + row_grp;
 #pragma unroll
   for (int f = 0; f < 4; ++f) {
-    short4v dpack, apack;
+    short4v ds, ad;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      int i = i0 + r;
-      int j = f * 16 + col_base;
+      int i = w.row + r;
+      int j = f * 16 + w.col;
       float dsv = 0.f, adv = 0.f;
       if (i < L && j < L) {
         float s = s_saved[idx4(b, h, i, j, H, L, L)];
@@ -224,69 +183,22 @@ hstu_attn_bwd_kernel(
           }
         }
       }
-      dpack[r] = bf16_bits(dsv);
-      apack[r] = bf16_bits(adv);
-      tile_store(dsn, i, j, dpack[r]);
+      ds[r] = bf16_bits(dsv);
+      ad[r] = bf16_bits(adv);
     }
-    int j = f * 16 + col_base;
-    tile_store(dst, j, i0, dpack);
-    tile_store(adt, j, i0, apack);
+    strip_stash(dsn, f, ds, w);
+    strip_stash_tr(dst, f, ds, w);
+    strip_stash_tr(adt, f, ad, w);
   }
-  __builtin_amdgcn_wave_barrier();
 
-  const int nfrag_d = (D + 15) / 16;
-  {  // dQ
-    float4v a4[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      if (f >= nfrag_d) break;
-      for (int kk = 0; kk < TILE; kk += 32) {
-        a4[f] = mfma_bf16(frag_load(dsn, strip, kk, lane),
-                          frag_load(kt, f * 16, kk, lane), a4[f]);
-      }
-    }
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      if (f >= nfrag_d) break;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int i = strip + row_grp + r;
-        int d = f * 16 + col_base;
-        if (i < L && d < D) {
-          dq_out[idx4(b, h, i, d, H, L, D)] = __float2bfloat16(a4[f][r]);
-        }
-      }
-    }
-  }
-  __syncthreads();
-
-  {  // dK, dV
-    float4v ak[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-    float4v av[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      if (f >= nfrag_d) break;
-      for (int kk = 0; kk < TILE; kk += 32) {
-        ak[f] = mfma_bf16(frag_load(dst, strip, kk, lane),
-                          frag_load(qt, f * 16, kk, lane), ak[f]);
-        av[f] = mfma_bf16(frag_load(adt, strip, kk, lane),
-                          frag_load(dot, f * 16, kk, lane), av[f]);
-      }
-    }
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      if (f >= nfrag_d) break;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int j = strip + row_grp + r;
-        int d = f * 16 + col_base;
-        if (j < L && d < D) {
-          dk_out[idx4(b, h, j, d, H, L, D)] = __float2bfloat16(ak[f][r]);
-          dv_out[idx4(b, h, j, d, H, L, D)] = __float2bfloat16(av[f][r]);
-        }
-      }
-    }
-  }
+  float4v ak[4] = {};
+  float4v av[4] = {};
+  strip_bwd_products(dsn, kt, dst, qt, adt, dot, (D + 15) / 16, ak, av, w,
+                     [&](const float4v (&aq)[4]) {
+                       strip_store(dq_out, bh, 0, L, D, aq, w);
+                     });
+  strip_store(dk_out, bh, 0, L, D, ak, w);
+  strip_store(dv_out, bh, 0, L, D, av, w);
 
   // flush bias histograms: one global atomicAdd per bucket per block
   __syncthreads();
@@ -315,7 +227,7 @@ std::vector<torch::Tensor> hstu_attn_fwd(
   auto s_saved = torch::empty({B, H, L, L},
                               q.options().dtype(torch::kFloat32));
   auto pb = pos_bucket.to(torch::kInt32).contiguous();
-  torch::Tensor ts64;
+  torch::Tensor ts64, pad_c;
   if (timestamps.has_value())
     ts64 = timestamps->to(torch::kInt64).contiguous();
   int n_time = time_table.has_value() ? time_table->size(0) : 0;
@@ -323,22 +235,15 @@ std::vector<torch::Tensor> hstu_attn_fwd(
   dim3 grid(B * H);
   size_t smem = 4 * TILE * 128;
   auto stream = at::cuda::getCurrentHIPStream();
-  hipLaunchKernelGGL((hstu_attn_fwd_kernel<__hip_bfloat16>), grid, block,
-      smem, stream,
-      reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
-      reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
-      reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()),
-      pb.data_ptr<int>(),
-      reinterpret_cast<const __hip_bfloat16*>(pos_table.data_ptr()),
-      time_table.has_value()
-          ? reinterpret_cast<const __hip_bfloat16*>(time_table->data_ptr())
-          : nullptr,
+  hipLaunchKernelGGL(hstu_attn_fwd_kernel, grid, block, smem, stream,
+      bf16_cptr(q), bf16_cptr(k), bf16_cptr(v), pb.data_ptr<int>(),
+      bf16_cptr(pos_table),
+      time_table.has_value() ? bf16_cptr(*time_table) : nullptr,
       timestamps.has_value()
           ? reinterpret_cast<const long long*>(ts64.data_ptr())
           : nullptr,
-      key_pad.has_value() ? key_pad->data_ptr<bool>() : nullptr,
-      reinterpret_cast<__hip_bfloat16*>(out.data_ptr()),
-      s_saved.data_ptr<float>(), B, H, L, D, n_time);
+      pad_ptr(key_pad, pad_c), bf16_ptr(out), s_saved.data_ptr<float>(),
+      B, H, L, D, n_time);
   return {out, s_saved};
 }
 
@@ -370,19 +275,13 @@ std::vector<torch::Tensor> hstu_attn_bwd(
   size_t smem = 8 * TILE * 128 +
                 ((size_t)n_pos + (size_t)n_time) * sizeof(float);
   auto stream = at::cuda::getCurrentHIPStream();
-  hipLaunchKernelGGL((hstu_attn_bwd_kernel<__hip_bfloat16>), grid, block,
-      smem, stream,
-      reinterpret_cast<const __hip_bfloat16*>(dc.data_ptr()),
-      reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
-      reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
-      reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()),
+  hipLaunchKernelGGL(hstu_attn_bwd_kernel, grid, block, smem, stream,
+      bf16_cptr(dc), bf16_cptr(q), bf16_cptr(k), bf16_cptr(v),
       s_saved.data_ptr<float>(), pb.data_ptr<int>(),
       timestamps.has_value()
           ? reinterpret_cast<const long long*>(ts64.data_ptr())
           : nullptr,
-      reinterpret_cast<__hip_bfloat16*>(dq.data_ptr()),
-      reinterpret_cast<__hip_bfloat16*>(dk.data_ptr()),
-      reinterpret_cast<__hip_bfloat16*>(dv.data_ptr()),
+      bf16_ptr(dq), bf16_ptr(dk), bf16_ptr(dv),
       dpos.data_ptr<float>(), dtime_ptr,
       B, H, L, D, (int)n_pos, (int)n_time);
   return {dq, dk, dv, dpos, dtime};

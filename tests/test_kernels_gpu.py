@@ -559,6 +559,71 @@ def test_hstu_fused_grads_vs_composed():
         _rel_err_ok(g_fused[n], p.grad, rel=0.08, frac=0.999)
 
 
+def _hstu_small_case(use_time, device):
+    """B=2, H=2, L=33, D=32: a ragged strip (33 = 2 * 16 + 1 rows), two of
+    the four head-dim fragments live, a key-pad tail on one batch item."""
+    from genrec_amd.models.hstu import RelativePositionBias
+
+    # seed and input scale chosen so that the bf16 composition itself stays
+    # within the bounds below against fp32 eager (checked on the CPU)
+    torch.manual_seed(23)
+    B, H, L, D = 2, 2, 33, 32
+    q, k, v = ((torch.randn(B, H, L, D) * 0.5).to(torch.bfloat16)
+               for _ in range(3))
+    pos_w = (torch.randn(32, H) * 0.5).to(torch.bfloat16)
+    time_w = (torch.randn(64, H) * 0.5).to(torch.bfloat16) if use_time \
+        else None
+    pb = RelativePositionBias(32, 128, H).bucket_table(L, "cpu")
+    ts = (torch.arange(L) * 3600 + 10 ** 9).unsqueeze(0).expand(B, -1) \
+        .contiguous()
+    pad = torch.zeros(B, L, dtype=torch.bool)
+    pad[1, 25:] = True
+    g = torch.randn(B, H, L, D).to(torch.bfloat16)
+    leaves = [t.to(device).requires_grad_(True)
+              for t in (q, k, v, pos_w) + ((time_w,) if use_time else ())]
+    return leaves, pb.to(device), ts.to(device), pad.to(device), g.to(device)
+
+
+def _hstu_composed(leaves, pb, ts, pad, g):
+    """hstu_pointwise_attention on the materialised bias tensors; returns
+    out and the gradients of the leaves."""
+    from genrec_amd import ops
+    from genrec_amd.ops.attention import hstu_pointwise_attention
+
+    q, k, v, pos_w = leaves[:4]
+    # materialised per batch item: the attention kernels index a 4-D bias
+    # as [B, H, L, L]
+    pos_bias = ops.embedding(pos_w, pb).permute(2, 0, 1).unsqueeze(0) \
+        .expand(q.size(0), -1, -1, -1)
+    time_bias = None
+    if len(leaves) == 5:
+        diff = ts.unsqueeze(2) - ts.unsqueeze(1)
+        tb = (torch.log(diff.abs().clamp(min=1).float()) / 0.693).long() \
+            .clamp(min=0, max=leaves[4].size(0) - 1)
+        time_bias = ops.embedding(leaves[4], tb).permute(0, 3, 1, 2)
+    out = hstu_pointwise_attention(q, k, v, pos_bias, time_bias, pad)
+    return out, torch.autograd.grad(out, leaves, g.to(out.dtype))
+
+
+@pytest.mark.parametrize("use_time", [False, True])
+def test_hstu_kernel_small_shape_vs_composed(use_time):
+    """hstu_attn_fwd / hstu_attn_bwd at L=33, D=32, with and without the
+    time table, vs the bias-tensor composition on the same bf16 inputs."""
+    from genrec_amd.ops.attention import hstu_fused_attention
+
+    leaves, pb, ts, pad, g = _hstu_small_case(use_time, DEV)
+    out = hstu_fused_attention(leaves[0], leaves[1], leaves[2], pb,
+                               leaves[3], leaves[4] if use_time else None,
+                               ts if use_time else None, pad)
+    assert out is not None, "the fused HSTU kernel must take this shape"
+    got = torch.autograd.grad(out, leaves, g)
+    ref_out, ref = _hstu_composed(leaves, pb, ts, pad, g)
+    for a, b in [(out, ref_out)] + list(zip(got, ref)):
+        assert torch.allclose(a.float(), b.float(), atol=0.5, rtol=0.1), \
+            (a.float() - b.float()).abs().max()
+        _rel_err_ok(a, b, rel=0.08, frac=0.999)
+
+
 def test_graph_step_equals_eager_step():
     """The hipGraph-captured train step must produce the same parameter
     updates as the eager step (proves no work is skipped in the captured
@@ -770,7 +835,8 @@ def test_mfma_attention_strided_views_match_contiguous():
 
 
 @pytest.mark.parametrize("case", ["plain128", "bias80", "causal128",
-                                  "padmask96", "dropout128", "plain130_d32"])
+                                  "padmask96", "dropout128", "plain130_d32",
+                                  "masks65"])
 def test_flash_attention_vs_eager(case):
     """Flash-tiled kernels (Lk>64) vs the eager fp32 reference. Default
     dispatch path for Lk>64 since round 2."""
@@ -778,10 +844,14 @@ def test_flash_attention_vs_eager(case):
 
     torch.manual_seed(0)
     B, H, D = 4, 3, (32 if case == "plain130_d32" else 64)
+    if case == "masks65":
+        B = 2
     Lq = {"plain128": 100, "bias80": 80, "causal128": 128,
-          "padmask96": 61, "dropout128": 90, "plain130_d32": 70}[case]
+          "padmask96": 61, "dropout128": 90, "plain130_d32": 70,
+          "masks65": 65}[case]
     Lk = {"plain128": 128, "bias80": 80, "causal128": 128,
-          "padmask96": 96, "dropout128": 128, "plain130_d32": 130}[case]
+          "padmask96": 96, "dropout128": 128, "plain130_d32": 130,
+          "masks65": 65}[case]
     q = torch.randn(B, H, Lq, D, device=DEV, dtype=torch.bfloat16,
                     requires_grad=True)
     k = torch.randn(B, H, Lk, D, device=DEV, dtype=torch.bfloat16,
@@ -797,6 +867,15 @@ def test_flash_attention_vs_eager(case):
         kp = torch.zeros(B, Lk, dtype=torch.bool, device=DEV)
         kp[:, -20:] = True
         kw["key_pad_mask"] = kp
+    if case == "masks65":
+        # query mask + 2-D additive mask + 4-D bf16 bias together
+        kw["bias"] = torch.randn(B, H, Lq, Lk, device=DEV,
+                                 dtype=torch.bfloat16, requires_grad=True)
+        kw["additive_mask"] = torch.randn(Lq, Lk, device=DEV)
+        qm = torch.ones(B, Lq, device=DEV)
+        qm[0, :7] = 0.0
+        qm[1, -3:] = 0.0
+        kw["query_mask"] = qm
     drop = 0.3 if case == "dropout128" else 0.0
 
     out = fused_attention(q, k, v, scale=0.125, dropout_p=drop,
@@ -829,6 +908,6 @@ def test_flash_attention_vs_eager(case):
     for a, b2 in ((q.grad, q2.grad), (k.grad, k2.grad), (v.grad, v2.grad)):
         assert torch.allclose(a.float(), b2, atol=8e-2, rtol=8e-2), \
             (a.float() - b2).abs().max()
-    if case == "bias80":
-        assert torch.allclose(kw["bias"].grad, kw2["bias"].grad,
+    if "bias" in kw:
+        assert torch.allclose(kw["bias"].grad.float(), kw2["bias"].grad,
                               atol=8e-2, rtol=8e-2)

@@ -5,7 +5,9 @@ staging V_t / K_t^T once, looping q-tiles (dO / dO^T / Q^T staged with
 the 8x8 butterfly), dA = dO V_t^T per wave, the P-reconstruction
 epilogue (dS = P*(M*dA - dot_i) with dot_i = rowsum(dO*O)), the
 dsn/dst/adt tile stores, and the three MFMAs (dQ per q-tile via
-atomics; dK/dV accumulated in registers across q-tiles). Compared
+atomics; dK/dV accumulated in registers across q-tiles). In the kernel
+the tile stores are strip_stash / strip_stash_tr and the dQ, barrier,
+dK/dV tail is strip_bwd_products (csrc/core/flash_strip.h). Compared
 against autograd. Run: python tools/emulate_flash_bwd.py
 """
 

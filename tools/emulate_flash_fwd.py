@@ -10,6 +10,10 @@ lane-mapping bug in the kernel's logic shows up here as a mismatch,
 without spending GPU time. (LDS XOR swizzling is omitted: it is a
 bijection within each row applied identically by stores and frag loads,
 proven separately; tiles are emulated at element granularity.)
+In the kernel the per-wave products, the P stash and the row store are the
+runtime strip steps of csrc/core/flash_strip.h (strip_mma, strip_stash,
+strip_store); `strip` / `row_grp` + `col` here are Strip::row0 / row / col
+there, and the staging index math is tile_chunk in mfma_tile.h.
 
 Run: python tools/emulate_flash_fwd.py
 """

@@ -165,6 +165,29 @@ def build_cases():
         return ops.ext().beam_attn_fwd(qb, kb, vb, padb, ksb, vsb, ancb, 3,
                                        sg, 2)
 
+    # HSTU pointwise attention: one ragged 64-tile, D=32, both bias tables,
+    # a key-pad tail on one batch item
+    Lh, Dh, n_pos, n_time = 50, 32, 32, 64
+    qh, kh, vh, douth = (torch.randn(B, 2, Lh, Dh, device=dev,
+                                     dtype=torch.bfloat16) for _ in range(4))
+    pbh = torch.randint(0, n_pos, (Lh, Lh), device=dev, dtype=torch.int32)
+    posw = torch.randn(n_pos, 2, device=dev, dtype=torch.bfloat16)
+    timew = torch.randn(n_time, 2, device=dev, dtype=torch.bfloat16)
+    tsh = (torch.arange(Lh, device=dev) * 3600 + 10 ** 9).unsqueeze(0) \
+        .expand(B, -1).contiguous()
+    padh = torch.zeros(B, Lh, dtype=torch.bool, device=dev)
+    padh[1, 40:] = True
+
+    def hstu_fwd():
+        return ops.ext().hstu_attn_fwd(qh, kh, vh, pbh, posw, timew, tsh,
+                                       padh)
+
+    hs = ops.ext().hstu_attn_fwd(qh, kh, vh, pbh, posw, timew, tsh, padh)[1]
+
+    def hstu_bwd():
+        return ops.ext().hstu_attn_bwd(douth, qh, kh, vh, hs, pbh, tsh,
+                                       n_pos, n_time)[:3]
+
     x = torch.randn(4096, 384, device=dev, dtype=torch.bfloat16)
     w = torch.randn(384, device=dev, dtype=torch.bfloat16)
 
@@ -262,6 +285,10 @@ def build_cases():
         ("gqa_varlen_fwd", gqa_varlen_fwd, 0.0),
         ("gqa_varlen_bwd", gqa_varlen_bwd, 0.0),
         ("beam_attn_fwd", beam_fwd, 0.0),
+        ("hstu_attn_fwd(out,s)", hstu_fwd, 0.0),
+        # dpos / dtime come from float LDS atomics (order-dependent
+        # rounding) and are left out; dq, dk, dv have none
+        ("hstu_attn_bwd(dq,dk,dv)", hstu_bwd, 0.0),
         ("rms_norm", rms, 0.0),
         ("layer_norm_fwd", ln_fwd, 0.0),
         ("layer_norm_bwd", ln_bwd, 0.0),
