@@ -144,6 +144,12 @@ torch::Tensor beam_attn_fwd(torch::Tensor q, torch::Tensor k_pre,
                             torch::Tensor k_suf, torch::Tensor v_suf,
                             torch::Tensor anc, int64_t t, double scale,
                             int64_t splits);
+torch::Tensor beam_attn_varlen_fwd(torch::Tensor q, torch::Tensor k_pre,
+                                   torch::Tensor v_pre,
+                                   torch::Tensor cu_seqlens,
+                                   int64_t max_prefix, torch::Tensor k_suf,
+                                   torch::Tensor v_suf, torch::Tensor anc,
+                                   int64_t t, double scale, int64_t splits);
 int64_t beam_attn_pick_splits(int64_t B, int64_t Hkv, int64_t rows,
                               int64_t Lp);
 
@@ -249,6 +255,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k_pre"), py::arg("v_pre"), py::arg("pre_pad"),
         py::arg("k_suf"), py::arg("v_suf"), py::arg("anc"), py::arg("t"),
         py::arg("scale"), py::arg("splits") = 0);
+  m.def("beam_attn_varlen_fwd", &genrec::beam_attn_varlen_fwd,
+        "beam-search decode attention over a packed prefill: k_pre/v_pre "
+        "[Ttot,Hkv,D], cu_seqlens int32 [B+1] -> out",
+        py::arg("q"), py::arg("k_pre"), py::arg("v_pre"),
+        py::arg("cu_seqlens"), py::arg("max_prefix"), py::arg("k_suf"),
+        py::arg("v_suf"), py::arg("anc"), py::arg("t"), py::arg("scale"),
+        py::arg("splits") = 0);
   m.def("beam_attn_pick_splits", &genrec::beam_attn_pick_splits,
         "prefix splits chosen for (B, Hkv, W*g rows, Lp)");
   m.def("add_rms_norm_fwd", &genrec::add_rms_norm_fwd,

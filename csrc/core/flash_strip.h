@@ -34,6 +34,46 @@ struct FlashView {
   }
 };
 
+// The batch item (fixed-length) or packed sequence (VARLEN) a block works
+// on, and where its rows sit in the operands and outputs.
+template <bool VARLEN>
+struct GqaSeq {
+  int Lq, Lk;  // lengths of this item
+  int b;
+  int start;   // first token of the sequence in the packed tensors
+  bool work;   // false: the block's tile lies beyond the sequence
+  // first row of the item in a [B,L,H,D] | [T,H,D] tensor
+  __device__ __forceinline__ int64_t tok0(int L) const {
+    return VARLEN ? (int64_t)start : (int64_t)b * L;
+  }
+  // first lse / delta entry of head h ([B,Hq,Lq] | [Hq,T])
+  __device__ __forceinline__ int64_t rowb(int h, int Hq, int T) const {
+    return VARLEN ? (int64_t)h * T + start : ((int64_t)b * Hq + h) * Lq;
+  }
+  // row 0 of head h of the item in operand x
+  __device__ __forceinline__ const __hip_bfloat16* rows(const FlashView& x,
+                                                        int h) const {
+    return x.p + (VARLEN ? (int64_t)start * x.l : (int64_t)b * x.b) +
+           (int64_t)h * x.h;
+  }
+};
+
+// tile0: first row of the block's Q (or K) tile. VARLEN reads the token
+// range of sequence b, clamped so that it lies inside [0,T]; work is
+// uniform per block, so a kernel may return on it before its first barrier.
+template <bool VARLEN>
+__device__ __forceinline__ GqaSeq<VARLEN> gqa_seq(const int* __restrict__ cu,
+                                                  int T, int b, int Lq, int Lk,
+                                                  int tile0) {
+  if constexpr (VARLEN) {
+    const int a = min(max(cu[b], 0), T);
+    const int e = min(max(cu[b + 1], a), T);
+    return {e - a, e - a, b, a, tile0 < e - a};
+  } else {
+    return {Lq, Lk, b, 0, true};
+  }
+}
+
 // Where a lane sits in its wave's strip.
 struct Strip {
   int lane;

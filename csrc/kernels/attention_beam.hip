@@ -23,6 +23,17 @@
 // Nothing is ever read from suffix slots s >= t or from anc[..., s >= t].
 // Padded prefix keys are staged as zeros, so whatever they hold (NaN
 // included) cannot reach the output through 0 * x.
+//
+// Variable-length prefix (VARLEN = true; beam_attn_varlen_fwd): k_pre/v_pre
+// are the token-major [Ttot,Hkv,D] K/V of a packed prefill and cu_seqlens
+// [B+1] (int32, device) gives prompt b the tokens [cu[b], cu[b+1]), clamped
+// by gqa_seq to [0,Ttot] and to end >= start, so no cu_seqlens content
+// addresses outside the tensors. There is no pad mask. A block's split
+// ranges come from its own prompt's length, so per prompt the tiles, splits
+// and fold order, and with them the bits, are those of the fixed-length
+// kernel on that prompt alone (B = 1, no pad, same split count). Splits
+// beyond a short prompt's tiles, and every split of an empty prompt, take
+// the empty-split exit; an empty prompt's rows then are the suffix softmax.
 
 #include <ATen/hip/HIPContext.h>
 
@@ -36,15 +47,16 @@ constexpr int BEAM_MAX_T = 16;
 
 // ------------------------------------------------------------ prefix phase
 
-template <int D>
+template <int D, bool VARLEN>
 __global__ void __launch_bounds__(256)
 beam_prefix_kernel(FlashView q,                       // [B*W,Hq,1,D]
-                   FlashView k, FlashView v,          // [B,Hkv,Lp,D]
+                   FlashView k, FlashView v,          // [B,Hkv,Lp,D] | [Ttot,Hkv,D]
                    const bool* __restrict__ pre_pad,  // null | [B,Lp]
                    float* __restrict__ ws_ml,         // [splits, rows, 2]
                    float* __restrict__ ws_acc,        // [splits, rows, D]
-                   int W, int Hq, int Hkv, int Lp, int qtiles,
-                   int64_t rows_total, float scale) {
+                   int W, int Hq, int Hkv, int Lp_max, int qtiles,
+                   int64_t rows_total, float scale,
+                   const int* __restrict__ cu, int Ttot) {  // VARLEN only
   constexpr int RS = D * 2;
   const int g = Hq / Hkv;
   const int n_rows = W * g;  // rows of this (prompt, KV head)
@@ -55,6 +67,11 @@ beam_prefix_kernel(FlashView q,                       // [B*W,Hq,1,D]
 
   const int tid = threadIdx.x;
   const Strip w(tid);
+
+  // this prompt's prefix: Lp_max keys, or (VARLEN) the clamped token range
+  // [cu[b], cu[b+1]) of the packed K/V; uniform per block
+  const GqaSeq<VARLEN> sq = gqa_seq<VARLEN>(cu, Ttot, b, Lp_max, Lp_max, 0);
+  const int Lp = sq.Lk;
 
   // this split's K tiles
   const int nkt = (Lp + TILE - 1) / TILE;
@@ -107,9 +124,10 @@ beam_prefix_kernel(FlashView q,                       // [B*W,Hq,1,D]
   RunningSoftmax sm;
   float4v accO[D / 16] = {};
 
-  const __hip_bfloat16* kb = k.p + (int64_t)b * k.b + (int64_t)hk * k.h;
-  const __hip_bfloat16* vb = v.p + (int64_t)b * v.b + (int64_t)hk * v.h;
-  const bool* pad = pre_pad ? pre_pad + (int64_t)b * Lp : nullptr;
+  const __hip_bfloat16* kb = sq.rows(k, hk);
+  const __hip_bfloat16* vb = sq.rows(v, hk);
+  const bool* pad =
+      (!VARLEN && pre_pad) ? pre_pad + (int64_t)b * Lp : nullptr;
 
   for (int kt0 = kt_begin; kt0 < kt_end; kt0 += TILE) {
     __syncthreads();  // previous iteration's ks/vt fully consumed
@@ -248,14 +266,16 @@ beam_combine_kernel(FlashView q,                               // [B*W,Hq,1,D]
 
 // ------------------------------------------------------------------ hosts
 
-template <int D>
+// k/v: [B,Hkv,Lp,D] with pad, or (VARLEN) token-major [Ttot,Hkv,D] with the
+// device offsets cu [B+1]; Lp then is only the host's upper bound.
+template <int D, bool VARLEN>
 void beam_launch(const torch::Tensor& q, const torch::Tensor& k,
                  const torch::Tensor& v, const bool* pad,
                  const torch::Tensor& k_suf, const torch::Tensor& v_suf,
                  const torch::Tensor& anc, torch::Tensor& ws_ml,
                  torch::Tensor& ws_acc, torch::Tensor& out, int B, int W,
                  int Hq, int Hkv, int Lp, int T, int t, int splits,
-                 float scale) {
+                 float scale, const int* cu, int Ttot) {
   auto stream = at::cuda::getCurrentHIPStream();
   const int g = Hq / Hkv;
   const int qtiles = (W * g + TILE - 1) / TILE;
@@ -264,9 +284,12 @@ void beam_launch(const torch::Tensor& q, const torch::Tensor& k,
   {
     dim3 grid((unsigned int)((int64_t)B * Hkv * qtiles), splits);
     size_t smem = 2 * TILE * D * 2 + D * 128 + TILE * 128;  // 56 KiB at 128
-    hipLaunchKernelGGL(beam_prefix_kernel<D>, grid, dim3(256), smem, stream,
-        qv, view_bhld(k), view_bhld(v), pad, ws_ml.data_ptr<float>(),
-        ws_acc.data_ptr<float>(), W, Hq, Hkv, Lp, qtiles, rows_total, scale);
+    const FlashView kv = VARLEN ? view_thd(k) : view_bhld(k);
+    const FlashView vv = VARLEN ? view_thd(v) : view_bhld(v);
+    hipLaunchKernelGGL((beam_prefix_kernel<D, VARLEN>), grid, dim3(256), smem,
+        stream, qv, kv, vv, pad, ws_ml.data_ptr<float>(),
+        ws_acc.data_ptr<float>(), W, Hq, Hkv, Lp, qtiles, rows_total, scale,
+        cu, Ttot);
     C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   {
@@ -294,14 +317,20 @@ int64_t beam_attn_pick_splits(int64_t B, int64_t Hkv, int64_t rows,
   return std::max<int64_t>(1, std::min<int64_t>(want, nkt));
 }
 
-// One beam-search decode step over a shared prompt prefix; see the header
-// comment. splits <= 0: pick. Returns out [B*W, 1, Hq, D].
-torch::Tensor beam_attn_fwd(torch::Tensor q, torch::Tensor k_pre,
-                            torch::Tensor v_pre,
-                            c10::optional<torch::Tensor> pre_pad,
-                            torch::Tensor k_suf, torch::Tensor v_suf,
-                            torch::Tensor anc, int64_t t, double scale,
-                            int64_t splits) {
+namespace {
+
+// What the two hosts share once each has checked its prefix layout and read
+// B, Hkv and the prefix length Lp (VARLEN: the host's upper bound) from it:
+// the checks of q, the suffix slots and anc, the split choice, the
+// workspaces and the launch. kn/vn are the kernel-readable prefix.
+template <bool VARLEN>
+torch::Tensor beam_run(const torch::Tensor& q, const torch::Tensor& k_pre,
+                       const torch::Tensor& v_pre, const torch::Tensor& kn,
+                       const torch::Tensor& vn, const bool* pad,
+                       const torch::Tensor& k_suf, const torch::Tensor& v_suf,
+                       const torch::Tensor& anc, int64_t B, int64_t Hkv,
+                       int64_t Lp, int64_t t, double scale, int64_t splits,
+                       const int* cu = nullptr, int Ttot = 0) {
   TORCH_CHECK(q.is_cuda() && k_pre.is_cuda() && v_pre.is_cuda() &&
                   k_suf.is_cuda() && v_suf.is_cuda() && anc.is_cuda(),
               "beam_attn: all tensors must be GPU tensors");
@@ -313,16 +342,13 @@ torch::Tensor beam_attn_fwd(torch::Tensor q, torch::Tensor k_pre,
               "beam_attn: q/k/v must be bfloat16");
   TORCH_CHECK(q.dim() == 4 && q.size(2) == 1,
               "beam_attn: q must be [B*W,Hq,1,D]");
-  TORCH_CHECK(k_pre.dim() == 4 && v_pre.sizes() == k_pre.sizes(),
-              "beam_attn: k_pre/v_pre must be [B,Hkv,Lp,D]");
   const int64_t BW = q.size(0), Hq = q.size(1), D = q.size(3);
-  const int64_t B = k_pre.size(0), Hkv = k_pre.size(1), Lp = k_pre.size(2);
   TORCH_CHECK(D == 64 || D == 128,
               "beam_attn: head dim must be 64 or 128, got ", D);
-  TORCH_CHECK(k_pre.size(3) == D, "beam_attn: k_pre head dim mismatch");
+  TORCH_CHECK(k_pre.size(-1) == D, "beam_attn: k_pre head dim mismatch");
   TORCH_CHECK(Hkv >= 1 && Hq % Hkv == 0, "beam_attn: Hq (", Hq,
               ") must be a multiple of Hkv (", Hkv, ")");
-  TORCH_CHECK(B >= 1 && Lp >= 1 && BW >= B && BW % B == 0,
+  TORCH_CHECK(B >= 1 && BW >= B && BW % B == 0,
               "beam_attn: q batch must be a multiple of the prompt batch");
   const int64_t W = BW / B;
   TORCH_CHECK(k_suf.dim() == 5 && k_suf.size(0) == B && k_suf.size(2) == W &&
@@ -338,18 +364,8 @@ torch::Tensor beam_attn_fwd(torch::Tensor q, torch::Tensor k_pre,
                   anc.is_contiguous(),
               "beam_attn: anc must be a contiguous int32 [B,W,T]");
   TORCH_CHECK(BW * Hq < (int64_t(1) << 31), "beam_attn: batch too large");
-  if (pre_pad.has_value()) {
-    TORCH_CHECK(pre_pad->is_cuda() &&
-                    pre_pad->scalar_type() == torch::kBool &&
-                    pre_pad->dim() == 2 && pre_pad->size(0) == B &&
-                    pre_pad->size(1) == Lp,
-                "beam_attn: pre_pad must be a bool [B,Lp] GPU tensor");
-  }
-  torch::Tensor padc;
-  const bool* pad = pad_ptr(pre_pad, padc);
   // q has one row per (beam, head): only k/v carry a row stride
-  torch::Tensor qn = kernel_readable(q, 2), kn = kernel_readable(k_pre, 3),
-                vn = kernel_readable(v_pre, 3);
+  torch::Tensor qn = kernel_readable(q, 2);
 
   const int64_t g = Hq / Hkv;
   int64_t S = splits > 0 ? splits : beam_attn_pick_splits(B, Hkv, W * g, Lp);
@@ -359,11 +375,73 @@ torch::Tensor beam_attn_fwd(torch::Tensor q, torch::Tensor k_pre,
   auto ws_acc = torch::empty({S, BW * Hq, D}, f32);
   auto out = torch::empty({BW, 1, Hq, D}, q.options());
   dispatch_head_dim(D, [&](auto d) {
-    beam_launch<decltype(d)::value>(qn, kn, vn, pad, k_suf, v_suf, anc, ws_ml,
-                                    ws_acc, out, B, W, Hq, Hkv, Lp, T, t, S,
-                                    (float)scale);
+    beam_launch<decltype(d)::value, VARLEN>(
+        qn, kn, vn, pad, k_suf, v_suf, anc, ws_ml, ws_acc, out, B, W, Hq, Hkv,
+        Lp, T, t, S, (float)scale, cu, Ttot);
   });
   return out;
+}
+
+}  // namespace
+
+// One beam-search decode step over a shared prompt prefix; see the header
+// comment. splits <= 0: pick. Returns out [B*W, 1, Hq, D].
+torch::Tensor beam_attn_fwd(torch::Tensor q, torch::Tensor k_pre,
+                            torch::Tensor v_pre,
+                            c10::optional<torch::Tensor> pre_pad,
+                            torch::Tensor k_suf, torch::Tensor v_suf,
+                            torch::Tensor anc, int64_t t, double scale,
+                            int64_t splits) {
+  TORCH_CHECK(k_pre.dim() == 4 && v_pre.sizes() == k_pre.sizes(),
+              "beam_attn: k_pre/v_pre must be [B,Hkv,Lp,D]");
+  const int64_t B = k_pre.size(0), Hkv = k_pre.size(1), Lp = k_pre.size(2);
+  TORCH_CHECK(Lp >= 1, "beam_attn: empty prefix");
+  if (pre_pad.has_value()) {
+    TORCH_CHECK(pre_pad->is_cuda() &&
+                    pre_pad->scalar_type() == torch::kBool &&
+                    pre_pad->dim() == 2 && pre_pad->size(0) == B &&
+                    pre_pad->size(1) == Lp,
+                "beam_attn: pre_pad must be a bool [B,Lp] GPU tensor");
+  }
+  torch::Tensor padc;
+  const bool* pad = pad_ptr(pre_pad, padc);
+  // [B,Hkv,Lp,D]: batch, head and row strides
+  return beam_run<false>(q, k_pre, v_pre, kernel_readable(k_pre, 3),
+                         kernel_readable(v_pre, 3), pad, k_suf, v_suf, anc, B,
+                         Hkv, Lp, t, scale, splits);
+}
+
+// The same step over a packed prefill: k_pre/v_pre are token-major
+// [Ttot,Hkv,D] views and prompt b owns the tokens [cu[b], cu[b+1]) of them,
+// clamped into [0,Ttot]. cu_seqlens stays on the device; max_prefix (a host
+// int, >= the longest prompt) only feeds the split choice. Per prompt the
+// result is bit-identical to beam_attn_fwd on that prompt alone (B = 1,
+// Lp = its length, no pre_pad) with the same splits.
+torch::Tensor beam_attn_varlen_fwd(torch::Tensor q, torch::Tensor k_pre,
+                                   torch::Tensor v_pre,
+                                   torch::Tensor cu_seqlens,
+                                   int64_t max_prefix, torch::Tensor k_suf,
+                                   torch::Tensor v_suf, torch::Tensor anc,
+                                   int64_t t, double scale, int64_t splits) {
+  TORCH_CHECK(k_pre.dim() == 3 && v_pre.sizes() == k_pre.sizes(),
+              "beam_attn: k_pre/v_pre must be [Ttot,Hkv,D]");
+  TORCH_CHECK(cu_seqlens.is_cuda() &&
+                  cu_seqlens.scalar_type() == torch::kInt32 &&
+                  cu_seqlens.dim() == 1 && cu_seqlens.numel() >= 2 &&
+                  cu_seqlens.is_contiguous() &&
+                  cu_seqlens.device() == k_pre.device(),
+              "beam_attn: cu_seqlens must be a contiguous int32 [B+1] tensor "
+              "on the device of k_pre");
+  const int64_t B = cu_seqlens.numel() - 1;
+  const int64_t Ttot = k_pre.size(0), Hkv = k_pre.size(1);
+  TORCH_CHECK(Ttot < (int64_t(1) << 31), "beam_attn: too many tokens");
+  TORCH_CHECK(max_prefix >= 0 && max_prefix < (int64_t(1) << 31),
+              "beam_attn: max_prefix out of range");
+  // [Ttot,Hkv,D]: token and head strides
+  return beam_run<true>(q, k_pre, v_pre, kernel_readable(k_pre, 2),
+                        kernel_readable(v_pre, 2), nullptr, k_suf, v_suf, anc,
+                        B, Hkv, max_prefix, t, scale, splits,
+                        cu_seqlens.data_ptr<int>(), (int)Ttot);
 }
 
 }  // namespace genrec

@@ -63,6 +63,7 @@ def _attn_kwargs(attn_implementation: Optional[str]) -> Dict[str, str]:
 LOSS_IMPLEMENTATIONS = (None, "genrec_lce")
 LAYER_IMPLEMENTATIONS = (None, "genrec_fused")
 BEAM_CACHES = (None, "shared_prefix")
+PREFILLS = (None, "packed")
 
 
 def _check_layer_implementation(layer_implementation: Optional[str]) -> None:
@@ -263,6 +264,7 @@ class LCRec(nn.Module):
         eos_token_id: Optional[int] = None,
         temperature: float = 1.0,
         beam_cache: Optional[str] = None,
+        prefill: Optional[str] = None,
     ) -> List[List[Tuple[torch.Tensor, float]]]:
         """Batched KV-cached constrained beam search.
 
@@ -272,6 +274,15 @@ class LCRec(nn.Module):
         lineage table (SharedPrefixBeamCache) and runs each decode step's
         attention through ops.beam_decode_attention. It needs
         attn_implementation="genrec_gqa" and max_new_tokens <= 16.
+
+        prefill: None prefills the left-padded batch as given. "packed"
+        (with beam_cache="shared_prefix") drops the pads on the device: the
+        real tokens of all prompts run as one [1,T] row with restarting
+        position ids (ops.gqa_varlen_attention), the cache keeps the
+        token-major K/V (SharedPrefixBeamCache.from_packed_prefill) and the
+        decode steps read each prompt's own length through
+        ops.beam_decode_varlen_attention. Arguments and return value are
+        the same; every prompt needs at least one real token.
 
         allowed_token_ids: per-step 1-D tensors of legal token ids (the
         device-mask replacement for the reference's per-token Python
@@ -283,6 +294,19 @@ class LCRec(nn.Module):
         if beam_cache not in BEAM_CACHES:
             raise ValueError(f"beam_cache {beam_cache!r}: expected one of "
                              f"{BEAM_CACHES}")
+        if prefill not in PREFILLS:
+            raise ValueError(f"prefill {prefill!r}: expected one of "
+                             f"{PREFILLS}")
+        if prefill == "packed":
+            if beam_cache != "shared_prefix":
+                raise ValueError(
+                    'prefill="packed" requires beam_cache="shared_prefix", '
+                    f"got {beam_cache!r}")
+            if self.attn_implementation != "genrec_gqa":
+                raise ValueError(
+                    'prefill="packed" requires '
+                    'attn_implementation="genrec_gqa", got '
+                    f"{self.attn_implementation!r}")
         if beam_cache == "shared_prefix":
             from genrec_amd.ops.attention import BEAM_MAX_SUFFIX
 
@@ -314,7 +338,38 @@ class LCRec(nn.Module):
         # prefill once per batch row; decode(last, step) -> [B*W, V] logits
         # of one step, hop(parent) moves the cache to the surviving beams
         cache = DynamicCache()
-        if beam_cache == "shared_prefix":
+        if prefill == "packed":
+            from genrec_amd.modules.hf_attention import SharedPrefixBeamCache
+
+            # the real tokens of every prompt as one row; offsets, ids and
+            # restarting positions are built on the device (the boolean
+            # gather is the one sync: T is the backbone's input shape)
+            real = attention_mask.bool()
+            lens = real.sum(dim=1)                            # [B]
+            cu = F.pad(lens.cumsum(0), (1, 0)).to(torch.int32)
+            flat_ids = input_ids[real].unsqueeze(0)           # [1, T]
+            flat_pos = (real.long().cumsum(1) - 1)[real].unsqueeze(0)
+            kw = self._packed_kwargs(flat_ids, flat_pos, cu, L)
+            kw["use_cache"] = True
+            out = self.model(input_ids=flat_ids, past_key_values=cache,
+                             logits_to_keep=cu[1:].long() - 1, **kw)
+            logits = out.logits[0] / temperature              # [B, V]
+            # L bounds every prompt's length without reading lens
+            beams = SharedPrefixBeamCache.from_packed_prefill(
+                cache, cu, L, W, max(max_new_tokens - 1, 1))
+            beam_len = lens.repeat_interleave(W).unsqueeze(1)  # [B*W, 1]
+
+            def decode(last: torch.Tensor, step: int) -> torch.Tensor:
+                out = self.model(input_ids=last,
+                                 attention_mask={"full_attention": None},
+                                 position_ids=beam_len + (step - 1),
+                                 past_key_values=beams,
+                                 use_cache=True, logits_to_keep=1,
+                                 genrec_beam_state=beams)
+                return out.logits[:, -1, :]
+
+            hop = beams.advance
+        elif beam_cache == "shared_prefix":
             from genrec_amd.modules.hf_attention import SharedPrefixBeamCache
 
             out = self.model(input_ids=input_ids,

@@ -22,6 +22,9 @@ Beam-search decode can hand the adapter a `SharedPrefixBeamCache` as the
 extra forward keyword `genrec_beam_state`: the step's attention then runs
 `ops.beam_decode_attention` on the cache's one-copy-per-prompt prefix and
 its per-beam suffix slots (LCRec.generate_topk, beam_cache="shared_prefix").
+A cache built from a packed prefill (`from_packed_prefill`, generate_topk's
+prefill="packed") holds token-major prompt K/V without pads and goes through
+`ops.beam_decode_varlen_attention`.
 
 Packed ("padding-free") training hands it transformers' own keywords
 `cu_seq_lens_q`, `cu_seq_lens_k`, `max_length_q`, `max_length_k` with one
@@ -37,8 +40,8 @@ from typing import List, Optional, Tuple
 import torch
 
 from genrec_amd.ops.attention import (
-    BEAM_MAX_SUFFIX, beam_decode_attention, gqa_flash_attention,
-    gqa_kernel_supported, gqa_varlen_attention,
+    BEAM_MAX_SUFFIX, beam_decode_attention, beam_decode_varlen_attention,
+    gqa_flash_attention, gqa_kernel_supported, gqa_varlen_attention,
 )
 
 NAME = "genrec_gqa"
@@ -54,6 +57,12 @@ class SharedPrefixBeamCache:
     layers) says whose slot-s entry beam w inherits, so a beam hop rewrites
     W*T integers instead of gathering every K/V tensor.
 
+    Packed form (from_packed_prefill): k_pre/v_pre are [Ttot,Hkv,D] views of
+    a packed prefill's K/V, prompt b owning tokens [cu_seqlens[b],
+    cu_seqlens[b+1]); max_prefix is a host upper bound of the prompt
+    lengths. There is no pre_pad. Suffix slots, anc, update and advance are
+    the same.
+
     Duck-types the part of `transformers.Cache` a decoder layer uses:
     `update(k, v, layer_idx)` and `get_seq_length()`. Per decode step: every
     layer's `update` copies the step's projections into slot `t`, attention
@@ -62,11 +71,22 @@ class SharedPrefixBeamCache:
 
     def __init__(self, k_pre: List[torch.Tensor], v_pre: List[torch.Tensor],
                  beam_width: int, max_suffix: int,
-                 pre_pad: Optional[torch.Tensor] = None) -> None:
+                 pre_pad: Optional[torch.Tensor] = None,
+                 cu_seqlens: Optional[torch.Tensor] = None,
+                 max_prefix: Optional[int] = None) -> None:
         if not 1 <= max_suffix <= BEAM_MAX_SUFFIX:
             raise ValueError(f"max_suffix {max_suffix}: expected 1.."
                              f"{BEAM_MAX_SUFFIX}")
-        B, Hkv, _, D = k_pre[0].shape
+        if cu_seqlens is None:
+            B, Hkv, _, D = k_pre[0].shape
+        else:
+            if pre_pad is not None or max_prefix is None:
+                raise ValueError("a packed prefix takes cu_seqlens and "
+                                 "max_prefix, and no pre_pad")
+            _, Hkv, D = k_pre[0].shape
+            B = cu_seqlens.numel() - 1
+        self.cu_seqlens = cu_seqlens              # [B+1] int32 | None
+        self.max_prefix = max_prefix
         self.k_pre, self.v_pre = list(k_pre), list(v_pre)
         self.pre_pad = pre_pad                    # [B, Lp] bool | None
         self.beam_width, self.max_suffix = beam_width, max_suffix
@@ -88,7 +108,27 @@ class SharedPrefixBeamCache:
                    [layer.values for layer in cache.layers],
                    beam_width, max_suffix, pre_pad)
 
+    @classmethod
+    def from_packed_prefill(cls, cache, cu_seqlens: torch.Tensor,
+                            max_prefix: int, beam_width: int,
+                            max_suffix: int):
+        """From the DynamicCache a packed [1,T] prefill filled: each layer's
+        [1,Hkv,T,D] keys/values become [T,Hkv,D] views, no copy."""
+        return cls([layer.keys[0].transpose(0, 1) for layer in cache.layers],
+                   [layer.values[0].transpose(0, 1)
+                    for layer in cache.layers],
+                   beam_width, max_suffix,
+                   cu_seqlens=cu_seqlens.to(torch.int32).contiguous(),
+                   max_prefix=int(max_prefix))
+
+    @property
+    def packed(self) -> bool:
+        return self.cu_seqlens is not None
+
     def get_seq_length(self, layer_idx: int = 0) -> int:
+        # packed: an upper bound; position ids are passed explicitly there
+        if self.packed:
+            return self.max_prefix + self.t
         return self.k_pre[layer_idx].size(2) + self.t
 
     def update(self, key_states: torch.Tensor, value_states: torch.Tensor,
@@ -154,9 +194,15 @@ def genrec_gqa_attention_forward(
                              "steps of full-attention layers only")
         scale = scaling if scaling is not None else query.size(-1) ** -0.5
         i, st = module.layer_idx, beam_state
-        out = beam_decode_attention(
-            query, st.k_pre[i], st.v_pre[i], st.k_suf[i], st.v_suf[i],
-            st.anc, st.t + 1, pre_pad=st.pre_pad, scale=scale)
+        if st.packed:
+            out = beam_decode_varlen_attention(
+                query, st.k_pre[i], st.v_pre[i], st.cu_seqlens,
+                st.max_prefix, st.k_suf[i], st.v_suf[i], st.anc, st.t + 1,
+                scale=scale)
+        else:
+            out = beam_decode_attention(
+                query, st.k_pre[i], st.v_pre[i], st.k_suf[i], st.v_suf[i],
+                st.anc, st.t + 1, pre_pad=st.pre_pad, scale=scale)
         return out, None                      # [B*W, 1, Hq, D]
 
     lq, lk = query.size(2), key.size(2)

@@ -91,6 +91,8 @@ from genrec_amd.ops.attention import (  # noqa: E402
     gqa_varlen_supported,
     beam_decode_attention,
     beam_decode_supported,
+    beam_decode_varlen_attention,
+    beam_decode_varlen_supported,
 )
 from genrec_amd.ops.cross_kv import (  # noqa: E402
     cross_attention_kv, cross_kv_eligible, project_cross_kv,
@@ -127,6 +129,8 @@ __all__ = [
     "gqa_varlen_supported",
     "beam_decode_attention",
     "beam_decode_supported",
+    "beam_decode_varlen_attention",
+    "beam_decode_varlen_supported",
     "project_cross_kv",
     "cross_attention_kv",
     "cross_kv_eligible",

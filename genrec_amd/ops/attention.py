@@ -725,3 +725,106 @@ def beam_decode_attention(
                                          pre_pad)
     return gqa_flash_attention(q, k, v, key_pad_mask=key_pad, scale=scale,
                                causal=True)
+
+
+def beam_decode_varlen_supported(q: Tensor, k_pre: Tensor, v_pre: Tensor,
+                                 cu_seqlens: Tensor, k_suf: Tensor,
+                                 v_suf: Tensor, anc: Tensor) -> bool:
+    """True iff beam_decode_varlen_attention would run the HIP kernel on
+    these inputs (GPU, bf16, k_pre/v_pre [Ttot,Hkv,D] with D in {64,128},
+    Hq % Hkv == 0, T <= 16, d innermost with 8-element-aligned strides,
+    cu_seqlens an integer [B+1] tensor on the same device, not disabled)."""
+    if os.environ.get("GENREC_DISABLE_ATTN_BEAM", "0") == "1":
+        return False
+    if not (q.dim() == 4 and k_pre.dim() == 3 and k_suf.dim() == 5
+            and anc.dim() == 3 and q.size(2) == 1
+            and cu_seqlens.dim() == 1 and cu_seqlens.numel() >= 2):
+        return False
+    if not (q.dtype == k_pre.dtype == v_pre.dtype == k_suf.dtype
+            == v_suf.dtype == torch.bfloat16):
+        return False
+    if cu_seqlens.is_floating_point() or cu_seqlens.dtype == torch.bool \
+            or cu_seqlens.device != q.device:
+        return False
+    B = cu_seqlens.numel() - 1
+    _, Hkv, D = k_pre.shape
+    if D not in GQA_HEAD_DIMS or q.size(3) != D or v_pre.shape != k_pre.shape:
+        return False
+    if Hkv == 0 or q.size(1) % Hkv != 0 or q.size(0) == 0 \
+            or q.size(0) % B != 0:
+        return False
+    T, W = k_suf.size(1), q.size(0) // B
+    if tuple(k_suf.shape) != (B, T, W, Hkv, D) or v_suf.shape != k_suf.shape \
+            or tuple(anc.shape) != (B, W, T) or not 1 <= T <= BEAM_MAX_SUFFIX:
+        return False
+    if not (k_suf.is_contiguous() and v_suf.is_contiguous()):
+        return False
+    for x, dims in ((q, (0, 1)), (k_pre, (0, 1)), (v_pre, (0, 1))):
+        if x.stride(-1) != 1 or any(x.stride(d) % 8 for d in dims) \
+                or x.data_ptr() % 16:
+            return False
+    return _kernel_available("beam_attn_varlen_fwd", q, k_pre, v_pre, k_suf,
+                             v_suf, anc)
+
+
+def _packed_prefix_to_padded(k_pre: Tensor, v_pre: Tensor, cu_seqlens: Tensor,
+                             max_prefix: int):
+    """-> (k, v [B,Hkv,Lp,D], pre_pad [B,Lp] bool) with Lp = max_prefix:
+    prompt b's tokens first, pads behind them. Device index arithmetic with
+    the kernel's clamp of the offsets; cu_seqlens is not read on the host."""
+    Ttot = k_pre.size(0)
+    Lp = max(int(max_prefix), 1)
+    cu = cu_seqlens.to(device=k_pre.device, dtype=torch.long)
+    start = cu[:-1].clamp(0, Ttot)
+    end = torch.maximum(cu[1:], start).clamp(max=Ttot)
+    idx = start[:, None] + torch.arange(Lp, device=k_pre.device)[None, :]
+    pad = idx >= end[:, None]
+    if Ttot == 0:
+        shape = (cu.numel() - 1, k_pre.size(1), Lp, k_pre.size(2))
+        return k_pre.new_zeros(shape), v_pre.new_zeros(shape), pad
+    idx = idx.clamp(max=Ttot - 1)
+    return k_pre[idx].transpose(1, 2), v_pre[idx].transpose(1, 2), pad
+
+
+def beam_decode_varlen_attention(
+    q: Tensor,           # [B*W, Hq, 1, D]
+    k_pre: Tensor,       # [Ttot, Hkv, D]   packed prefill, token-major
+    v_pre: Tensor,       # [Ttot, Hkv, D]
+    cu_seqlens: Tensor,  # [B+1] int32 on q's device
+    max_prefix: int,     # host int >= the longest prompt
+    k_suf: Tensor,       # [B, T, W, Hkv, D]
+    v_suf: Tensor,       # [B, T, W, Hkv, D]
+    anc: Tensor,         # [B, W, T] int
+    t: int,
+    *,
+    scale: float,
+    _splits: int = 0,
+) -> Tensor:
+    """beam_decode_attention over the K/V of a packed (padding-free)
+    prefill -> [B*W, 1, Hq, D].
+
+    Prompt b owns tokens [cu_seqlens[b], cu_seqlens[b+1]) of k_pre/v_pre,
+    clamped into [0, Ttot]; there are no pad keys to mask or to stage. On the
+    kernel, max_prefix only picks the split count and cu_seqlens is never
+    read on the host; per prompt the result is bit-identical to
+    beam_decode_attention on that prompt alone with the same _splits. A
+    prompt of length 0 attends to its beams' suffixes only. GPU inputs the
+    kernel does not cover are scattered into [B,Hkv,max_prefix,D] plus a
+    pad mask on the device and go through beam_decode_attention.
+    """
+    if beam_decode_varlen_supported(q, k_pre, v_pre, cu_seqlens, k_suf,
+                                    v_suf, anc):
+        from genrec_amd import ops
+
+        return ops.ext().beam_attn_varlen_fwd(
+            q, k_pre, v_pre, cu_seqlens.to(torch.int32).contiguous(),
+            int(max_prefix), k_suf, v_suf,
+            anc.to(torch.int32).contiguous(), int(t), float(scale),
+            int(_splits))
+    if not q.is_cuda:
+        return eager.beam_decode_varlen_attention(
+            q, k_pre, v_pre, cu_seqlens, max_prefix, k_suf, v_suf, anc, t,
+            scale=scale)
+    k, v, pad = _packed_prefix_to_padded(k_pre, v_pre, cu_seqlens, max_prefix)
+    return beam_decode_attention(q, k, v, k_suf, v_suf, anc, t, pre_pad=pad,
+                                 scale=scale, _splits=_splits)

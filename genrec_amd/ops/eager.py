@@ -221,6 +221,40 @@ def beam_decode_attention(
                          causal=True)
 
 
+def beam_decode_varlen_attention(
+    q: Tensor,           # [B*W, Hq, 1, D]
+    k_pre: Tensor,       # [Ttot, Hkv, D] packed prefill, token-major
+    v_pre: Tensor,       # [Ttot, Hkv, D]
+    cu_seqlens: Tensor,  # [B+1] int, prompt b = tokens [cu[b], cu[b+1])
+    max_prefix: int,     # unused: the lengths are read from cu_seqlens
+    k_suf: Tensor,       # [B, T, W, Hkv, D]
+    v_suf: Tensor,       # [B, T, W, Hkv, D]
+    anc: Tensor,         # [B, W, T] int
+    t: int,
+    *,
+    scale: float,
+) -> Tensor:
+    """beam_decode_attention over a packed prefill, fp32 math
+    -> [B*W, 1, Hq, D]: a per-prompt loop over slices of the packed K/V
+    (reads cu_seqlens on the host). Offsets are clamped to [0, Ttot] and to
+    end >= start as the kernel clamps them; an empty prompt's beams attend
+    to their suffix only."""
+    B = cu_seqlens.numel() - 1
+    W = q.size(0) // B
+    Ttot = k_pre.size(0)
+    cu = cu_seqlens.tolist()
+    outs = []
+    for b in range(B):
+        s = min(max(int(cu[b]), 0), Ttot)
+        e = min(max(int(cu[b + 1]), s), Ttot)
+        outs.append(beam_decode_attention(
+            q[b * W:(b + 1) * W],
+            k_pre[s:e].transpose(0, 1).unsqueeze(0),
+            v_pre[s:e].transpose(0, 1).unsqueeze(0),
+            k_suf[b:b + 1], v_suf[b:b + 1], anc[b:b + 1], t, scale=scale))
+    return torch.cat(outs, dim=0)
+
+
 def pairwise_sqdist(x: Tensor, codebook: Tensor) -> Tensor:
     """L2 distance matrix ||x||^2 + ||c||^2 - 2 x c^T (ref rqvae.py:186-192)."""
     return (

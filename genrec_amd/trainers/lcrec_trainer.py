@@ -139,7 +139,8 @@ def extract_sem_ids(text: str, n_codebooks: int) -> Optional[List[int]]:
 def evaluate_aux_tasks(model: LCRec, metas, device,
                        helper: ConstrainedDecodingHelper, n_codebooks: int,
                        max_samples: int = 64,
-                       beam_cache: Optional[str] = None) -> Dict[str, float]:
+                       beam_cache: Optional[str] = None,
+                       prefill: Optional[str] = None) -> Dict[str, float]:
     """item2index greedy accuracy + index2item substring match
     (ref lcrec_trainer.py:190-222)."""
     from genrec_amd.data.lcrec_sft import TEMPLATES, sem_ids_to_tokens
@@ -162,7 +163,7 @@ def evaluate_aux_tasks(model: LCRec, metas, device,
                               .to(device),
                               max_new_tokens=n_codebooks, beam_width=1,
                               allowed_token_ids=allowed,
-                              beam_cache=beam_cache)
+                              beam_cache=beam_cache, prefill=prefill)
     L = ids.size(1)
     for m, row in zip(metas, res):
         text = model.decode(row[0][0][L:], skip_special_tokens=False)
@@ -175,14 +176,16 @@ def evaluate_aux_tasks(model: LCRec, metas, device,
                         model, for_generation=True)
     ids = batch["input_ids"].to(device)
     # free generation runs past the shared-prefix cache's suffix slots
-    # (and one beam has nothing to share): it keeps the default cache
+    # (and one beam has nothing to share): it keeps the default cache,
+    # and with it the padded prefill
     free_len = 24
+    shared = free_len <= BEAM_MAX_SUFFIX
     res = model.generate_topk(ids,
                               attention_mask=batch["attention_mask"]
                               .to(device),
                               max_new_tokens=free_len, beam_width=1,
-                              beam_cache=beam_cache
-                              if free_len <= BEAM_MAX_SUFFIX else None)
+                              beam_cache=beam_cache if shared else None,
+                              prefill=prefill if shared else None)
     L = ids.size(1)
     for m, row in zip(metas, res):
         text = model.decode(row[0][0][L:], skip_special_tokens=True)
@@ -198,7 +201,8 @@ def evaluate(model: LCRec, loader, device, helper: ConstrainedDecodingHelper,
              max_batches: Optional[int] = None,
              aux_tasks: bool = True,
              debug_logging: bool = False,
-             beam_cache: Optional[str] = None) -> Dict[str, float]:
+             beam_cache: Optional[str] = None,
+             prefill: Optional[str] = None) -> Dict[str, float]:
     model.eval()
     acc = TopKAccumulator(ks=list(ks))
     allowed = helper.allowed_token_ids()
@@ -214,7 +218,7 @@ def evaluate(model: LCRec, loader, device, helper: ConstrainedDecodingHelper,
         res = model.generate_topk(
             ids, attention_mask=attn, max_new_tokens=n_codebooks,
             beam_width=beam_width, allowed_token_ids=allowed,
-            beam_cache=beam_cache)
+            beam_cache=beam_cache, prefill=prefill)
         L = ids.size(1)
         preds, tgts = [], []
         for b, row in enumerate(res):
@@ -237,7 +241,8 @@ def evaluate(model: LCRec, loader, device, helper: ConstrainedDecodingHelper,
     metrics = acc.reduce(all_reduce=True)
     if aux_tasks:
         aux = evaluate_aux_tasks(model, aux_metas, device, helper,
-                                 n_codebooks, beam_cache=beam_cache)
+                                 n_codebooks, beam_cache=beam_cache,
+                                 prefill=prefill)
         aux = reduce_scalars(aux, device)
         t = max(aux.pop("aux_total"), 1.0)
         metrics["item2index_acc"] = aux["item2index_correct"] / t
@@ -302,8 +307,11 @@ def train(
     # = one prompt copy + per-beam suffix slots (needs "genrec_gqa")
     beam_cache: Optional[str] = None,
     # True = padding-free SFT: each batch's samples packed into one [1,T]
-    # row (needs "genrec_gqa"); evaluation and generation stay left-padded
+    # row (needs "genrec_gqa"); evaluation has its own switch, prefill
     packing: bool = False,
+    # None = evaluation prefills the left-padded prompts; "packed" = it
+    # drops the pads (needs beam_cache="shared_prefix")
+    prefill: Optional[str] = None,
 ):
     if max_length is not None:
         max_seq_len = max_length
@@ -371,7 +379,7 @@ def train(
                            beam_width=eval_beam_width,
                            max_batches=eval_max_batches,
                            debug_logging=debug_logging,
-                           beam_cache=beam_cache)
+                           beam_cache=beam_cache, prefill=prefill)
         if ctx.is_main:
             logger.info("eval-only %s", metrics)
         wb.finish()
@@ -420,7 +428,7 @@ def train(
                                n_codebooks, beam_width=eval_beam_width,
                                max_batches=eval_max_batches,
                                debug_logging=debug_logging,
-                               beam_cache=beam_cache)
+                               beam_cache=beam_cache, prefill=prefill)
             if ctx.is_main:
                 logger.info("epoch %d eval %s", epoch, metrics)
                 wb.log({f"eval/{k}": v for k, v in metrics.items()})

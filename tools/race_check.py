@@ -165,6 +165,16 @@ def build_cases():
         return ops.ext().beam_attn_fwd(qb, kb, vb, padb, ksb, vsb, ancb, 3,
                                        sg, 2)
 
+    # the same step over a packed prefill: the prompts' K/V as one
+    # token-major row, starts off the tile grid, lengths 130 and 67 (the
+    # second prompt has fewer tiles than there are splits: 3)
+    kbv, vbv = (t.transpose(1, 2).reshape(Bb * Lg, 2, Dg) for t in (kb, vb))
+    cub = torch.tensor([3, 133, 200], dtype=torch.int32, device=dev)
+
+    def beam_varlen_fwd():
+        return ops.ext().beam_attn_varlen_fwd(qb, kbv, vbv, cub, Lg, ksb, vsb,
+                                              ancb, 3, sg, 3)
+
     # HSTU pointwise attention: one ragged 64-tile, D=32, both bias tables,
     # a key-pad tail on one batch item
     Lh, Dh, n_pos, n_time = 50, 32, 32, 64
@@ -285,6 +295,7 @@ def build_cases():
         ("gqa_varlen_fwd", gqa_varlen_fwd, 0.0),
         ("gqa_varlen_bwd", gqa_varlen_bwd, 0.0),
         ("beam_attn_fwd", beam_fwd, 0.0),
+        ("beam_attn_varlen_fwd", beam_varlen_fwd, 0.0),
         ("hstu_attn_fwd(out,s)", hstu_fwd, 0.0),
         # dpos / dtime come from float LDS atomics (order-dependent
         # rounding) and are left out; dq, dk, dv have none
