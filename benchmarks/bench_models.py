@@ -134,7 +134,7 @@ def bench_rqvae(device, steps, warmup):
 
 def bench_lcrec(device, steps, warmup, full_size=False, attn_impl="sdpa",
                 loss_impl="hf", vocab=None, response_tokens=None,
-                eager_step=False, layer_impl="hf"):
+                eager_step=False, layer_impl="hf", lora="none"):
     """LCRec SFT step: Qwen2-1.5B-shaped backbone (lcrec/amazon/lcrec.gin:
     B=32, L=512, bf16, grad ckpt) — full size only on GPU. attn_impl selects
     the backbone attention ("sdpa" | "genrec_gqa") and loss_impl the loss
@@ -145,10 +145,17 @@ def bench_lcrec(device, steps, warmup, full_size=False, attn_impl="sdpa",
     sample, as sft_collate does (default: every position, as before).
     `eager_step` launches the step without hipGraph capture, as
     lcrec_trainer does; only then can "genrec_lce" drop the unsupervised
-    rows (the compaction needs one host sync)."""
+    rows (the compaction needs one host sync). `lora` adapts the seven
+    projections of every layer with the reference's defaults (r=16,
+    alpha=32, dropout=0.05) and trains the adapters only: "genrec" through
+    ops.lora_linear, "compose" through the stock op composition (dropout,
+    two F.linear, scale, add); the step is then launched eagerly (the
+    adapter dropout draws a host seed per call)."""
     from genrec_amd.models.lcrec import LCRec, default_qwen_config
 
     torch.manual_seed(0)
+    if lora != "none":
+        eager_step = True
     B, L = (32, 512) if full_size else (2, 64)
     cfg = default_qwen_config() if full_size else default_qwen_config(
         vocab_size=2048, hidden_size=256, num_layers=4, num_heads=8,
@@ -165,6 +172,15 @@ def bench_lcrec(device, steps, warmup, full_size=False, attn_impl="sdpa",
         # add_codebook_tokens resized to the offline tokenizer's length
         model.model.resize_token_embeddings(vocab + 5 * 256)
         model.model.config.vocab_size = vocab + 5 * 256
+    if lora != "none":
+        model.apply_lora()
+        if lora == "compose":
+            from genrec_amd.modules.lora import LoRALinear
+
+            composed = _composed_lora_class()
+            for m in model.modules():
+                if isinstance(m, LoRALinear):
+                    m.__class__ = composed
     if full_size:
         model.gradient_checkpointing_enable()
     model = model.to(device)
@@ -193,11 +209,28 @@ def bench_lcrec(device, steps, warmup, full_size=False, attn_impl="sdpa",
         if device.type == "cuda" else None
     return dict(model="lcrec-qwen2-1.5b" if full_size else "lcrec-tiny",
                 attn=attn_impl, loss=loss_impl, layers=layer_impl, vocab=V,
+                lora=lora,
+                trainable_params=sum(p.numel() for p in model.parameters()
+                                     if p.requires_grad),
                 step="eager" if eager_step else "graph",
                 supervised_per_sample=response_tokens or L,
                 batch=B, seq_len=L, samples_per_s=B * steps / el,
                 tokens_per_s=B * L * steps / el,
                 ms_per_step=el / steps * 1e3, peak_hbm_gib=peak)
+
+
+def _composed_lora_forward(self, x):
+    """peft's op order: base(x) + lora_B(lora_A(dropout(x))) * scaling"""
+    F = torch.nn.functional
+    xd = F.dropout(x, self.lora_dropout, self.training)
+    return self.base_layer(x) + self.lora_B(self.lora_A(xd)) * self.scaling
+
+
+def _composed_lora_class():
+    from genrec_amd.modules.lora import LoRALinear
+
+    return type("_ComposedLoRALinear", (LoRALinear,),
+                {"forward": _composed_lora_forward})
 
 
 class _PackedStep(torch.nn.Module):
@@ -347,6 +380,9 @@ def main():
                         "(Qwen2.5: 151936)")
     p.add_argument("--lcrec-response-tokens", type=int, default=None,
                    help="supervise only the last K positions per sample")
+    p.add_argument("--lcrec-lora", choices=["none", "compose", "genrec"],
+                   default="none",
+                   help="LoRA adapters on the LCRec step (forces eager)")
     p.add_argument("--lcrec-eager", action="store_true",
                    help="no hipGraph capture of the LCRec step")
     p.add_argument("--lcrec-packing", action="store_true",
@@ -368,6 +404,7 @@ def main():
             kw["vocab"] = args.lcrec_vocab
             kw["response_tokens"] = args.lcrec_response_tokens
             kw["eager_step"] = args.lcrec_eager
+            kw["lora"] = args.lcrec_lora
         bench = BENCHES[name]
         if name == "lcrec" and args.lcrec_packing:
             bench = bench_lcrec_packing

@@ -167,6 +167,15 @@ torch::Tensor swiglu_fwd(torch::Tensor gate, torch::Tensor up);
 std::vector<torch::Tensor> swiglu_bwd(torch::Tensor dy, torch::Tensor gate,
                                       torch::Tensor up);
 
+torch::Tensor lora_down(torch::Tensor x, torch::Tensor p_mat, double c,
+                        double drop_p, int64_t seed);
+torch::Tensor lora_up_add_(torch::Tensor y, torch::Tensor t, torch::Tensor q,
+                           double c, double drop_p, int64_t seed);
+torch::Tensor lora_grad(torch::Tensor t, torch::Tensor x, double c,
+                        double drop_p, int64_t seed);
+torch::Tensor lora_dropout_mask(int64_t M, int64_t Kw, double p,
+                                int64_t seed);
+
 }  // namespace genrec
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -279,4 +288,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("swiglu_fwd", &genrec::swiglu_fwd, "silu(gate) * up");
   m.def("swiglu_bwd", &genrec::swiglu_bwd,
         "silu(gate) * up backward, recomputed -> (dgate, dup)");
+  m.def("lora_down", &genrec::lora_down,
+        "T[M,r] = bf16(c * (mask.x)[M,Kw] @ p_mat[r,Kw]^T), r in 16/32/64",
+        py::arg("x"), py::arg("p_mat"), py::arg("c") = 1.0,
+        py::arg("drop_p") = 0.0, py::arg("seed") = 0);
+  m.def("lora_up_add_", &genrec::lora_up_add_,
+        "in place: y[M,Kw] = bf16(y + c * mask.(t[M,r] @ q[Kw,r]^T)) -> y",
+        py::arg("y"), py::arg("t"), py::arg("q"), py::arg("c") = 1.0,
+        py::arg("drop_p") = 0.0, py::arg("seed") = 0);
+  m.def("lora_grad", &genrec::lora_grad,
+        "G[r,Kw] = bf16(c * t[M,r]^T @ (mask.x)[M,Kw]) (deterministic)",
+        py::arg("t"), py::arg("x"), py::arg("c") = 1.0,
+        py::arg("drop_p") = 0.0, py::arg("seed") = 0);
+  m.def("lora_dropout_mask", &genrec::lora_dropout_mask,
+        "uint8 [M,Kw] keep mask of the lora kernels (tests only)",
+        py::arg("M"), py::arg("Kw"), py::arg("p"), py::arg("seed"));
 }

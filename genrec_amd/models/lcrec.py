@@ -237,7 +237,29 @@ class LCRec(nn.Module):
             shifted.reshape(-1), ignore_index=-100)
         return CausalLMOutputWithPast(loss=loss, logits=None)
 
+    def apply_lora(self, **kw) -> int:
+        """Freeze the backbone and wrap its projections in LoRA adapters
+        (genrec_amd.modules.lora.apply_lora; same keyword arguments).
+        Returns the number of wrapped modules."""
+        from genrec_amd.modules import lora
+
+        wrapped = lora.apply_lora(self.model, **kw)
+        self.lora_config = lora.lora_config(self.model)
+        return wrapped
+
     def save_pretrained(self, save_dir: str, **kwargs):
+        """With adapters on, the checkpoint is the merged model in the plain
+        transformers layout (load_pretrained and eval_only read it as any
+        other) and the adapter files are written next to it."""
+        from genrec_amd.modules import lora
+
+        if lora.lora_config(self.model) is not None:
+            self.model.save_pretrained(
+                save_dir, state_dict=lora.merged_state_dict(self.model),
+                **kwargs)
+            lora.save_adapter(self.model, save_dir)
+            self.tokenizer.save_pretrained(save_dir)
+            return
         self.model.save_pretrained(save_dir, **kwargs)
         self.tokenizer.save_pretrained(save_dir)
 

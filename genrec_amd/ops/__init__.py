@@ -107,6 +107,7 @@ from genrec_amd.ops.fused import (  # noqa: E402
     dropout_add, dropout_add_rms_norm, plain_dropout, relu_dropout,
 )
 from genrec_amd.ops.llm_layer import add_rms_norm, rope_qk, swiglu  # noqa: E402
+from genrec_amd.ops.lora import lora_linear  # noqa: E402
 
 __all__ = [
     "ext",
@@ -148,4 +149,5 @@ __all__ = [
     "add_rms_norm",
     "rope_qk",
     "swiglu",
+    "lora_linear",
 ]

@@ -486,3 +486,139 @@ def rope_qk(q: Tensor, k: Tensor, cos: Tensor,
 def swiglu(gate: Tensor, up: Tensor) -> Tensor:
     """Qwen2MLP's act_fn(gate) * up with the silu activation."""
     return F.silu(gate) * up
+
+
+# ---- LoRA-adapted linear (ops/lora.py). The three products below are the
+# torch forms of the csrc/kernels/lora.hip kernels, same signatures and the
+# same rounding points: products accumulate in fp32 (the operands' own
+# dtype for fp32 / fp64), T and G are rounded once to the operand dtype,
+# up_add adds the fp32 product to the upcast Y and rounds once, the mask
+# zeroes elements and c multiplies the fp32 product.
+
+_U64 = 1 << 64
+
+
+def _s64(c: int) -> int:
+    """c mod 2^64 as the int64 with the same bits."""
+    c %= _U64
+    return c - _U64 if c >= (1 << 63) else c
+
+
+def _lsr(z: Tensor, n: int) -> Tensor:
+    """logical right shift of int64 bit patterns"""
+    return (z >> n) & ((1 << (64 - n)) - 1)
+
+
+def lora_dropout_mask(M: int, Kw: int, p: float, seed: int,
+                      device=None) -> Tensor:
+    """uint8 [M, Kw] keep mask of the lora kernels, bit for bit: hash_rng
+    (csrc/core/common.h) of the position row * Kw + col in wrapping int64
+    arithmetic, keep iff its low 24 bits are >= float32(p) * 2^24."""
+    idx = torch.arange(M * Kw, dtype=torch.int64, device=device)
+    s1 = ((int(seed) & 0xFFFFFFFF) + 1) & 0xFFFFFFFF
+    z = idx + _s64(0x9E3779B97F4A7C15 * s1)
+    z = (z ^ _lsr(z, 30)) * _s64(0xBF58476D1CE4E5B9)
+    z = (z ^ _lsr(z, 27)) * _s64(0x94D049BB133111EB)
+    h = (z ^ _lsr(z, 31)) & 0xFFFFFF
+    thresh = int(torch.tensor(p, dtype=torch.float32).item() * 16777216.0)
+    return (h >= thresh).to(torch.uint8).view(M, Kw)
+
+
+def _lora_acc(dtype: torch.dtype) -> torch.dtype:
+    return torch.float32 if dtype in (torch.bfloat16, torch.float16) \
+        else dtype
+
+
+def _lora_masked(x: Tensor, p: float, seed: int) -> Tensor:
+    if p <= 0.0:
+        return x
+    keep = lora_dropout_mask(x.size(0), x.size(1), p, seed, x.device)
+    return x * keep.to(x.dtype)
+
+
+def lora_down(x: Tensor, p_mat: Tensor, c: float = 1.0, drop_p: float = 0.0,
+              seed: int = 0) -> Tensor:
+    """T[M,r] = round(c * (mask.x)[M,Kw] @ p_mat[r,Kw]^T)"""
+    acc = _lora_acc(x.dtype)
+    xm = _lora_masked(x, drop_p, seed)
+    return (c * (xm.to(acc) @ p_mat.to(acc).t())).to(x.dtype)
+
+
+def lora_up_add_(y: Tensor, t: Tensor, q: Tensor, c: float = 1.0,
+                 drop_p: float = 0.0, seed: int = 0) -> Tensor:
+    """in place: y[M,Kw] = round(y + c * mask.(t[M,r] @ q[Kw,r]^T))"""
+    acc = _lora_acc(y.dtype)
+    d = _lora_masked(c * (t.to(acc) @ q.to(acc).t()), drop_p, seed)
+    y.copy_((y.to(acc) + d).to(y.dtype))
+    return y
+
+
+def lora_grad(t: Tensor, x: Tensor, c: float = 1.0, drop_p: float = 0.0,
+              seed: int = 0) -> Tensor:
+    """G[r,Kw] = round(c * t[M,r]^T @ (mask.x)[M,Kw])"""
+    acc = _lora_acc(x.dtype)
+    xm = _lora_masked(x, drop_p, seed)
+    return (c * (t.to(acc).t() @ xm.to(acc))).to(x.dtype)
+
+
+class LoRALinearFn(torch.autograd.Function):
+    """y = x W^T + b + s * (drop(x) A^T) B^T as one node. `impl` supplies
+    lora_down / lora_up_add_ / lora_grad: this module (torch) or the
+    compiled extension (HIP); everything else is shared. Saves x, the
+    rank-r activation t and the seed, never a mask; the base weight's and
+    bias's gradients are computed only when asked for."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, lora_a, lora_b, scaling, p, seed, impl):
+        K, N = weight.size(1), weight.size(0)
+        y = F.linear(x, weight, bias)
+        x2 = impl.lora_rows(x, K)
+        inv_keep = 1.0 / (1.0 - p) if p > 0.0 else 1.0
+        t = impl.lora_down(x2, lora_a, inv_keep, p, seed)
+        impl.lora_up_add_(y.view(-1, N), t, lora_b, scaling, 0.0, 0)
+        ctx.save_for_backward(x2, t, weight, lora_a, lora_b)
+        ctx.cfg = (scaling, p, seed, inv_keep, impl, x.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, t, weight, lora_a, lora_b = ctx.saved_tensors
+        scaling, p, seed, inv_keep, impl, x_shape = ctx.cfg
+        need = ctx.needs_input_grad
+        dy2 = impl.lora_rows(dy, weight.size(0))
+        dt = impl.lora_down(dy2, lora_b.t().contiguous(), scaling, 0.0, 0)
+        d_a = d_b = dx = dw = dbias = None
+        if need[4]:
+            d_b = impl.lora_grad(t, dy2, scaling, 0.0, 0).t().contiguous()
+        if need[3]:
+            d_a = impl.lora_grad(dt, x2, inv_keep, p, seed)
+        if need[0]:
+            dx2 = dy2 @ weight
+            impl.lora_up_add_(dx2, dt, lora_a.t().contiguous(), inv_keep, p,
+                              seed)
+            dx = dx2.view(x_shape)
+        if need[1]:
+            dw = dy2.t() @ x2
+        if need[2]:
+            dbias = dy2.sum(0)
+        return dx, dw, dbias, d_a, d_b, None, None, None, None
+
+
+def lora_rows(t: Tensor, width: int) -> Tensor:
+    """t as [rows, width]"""
+    return t.reshape(-1, width)
+
+
+def lora_linear(x: Tensor, weight: Tensor, bias: Optional[Tensor],
+                lora_a: Tensor, lora_b: Tensor, scaling: float,
+                p: float = 0.0, training: bool = False,
+                seed: Optional[int] = None) -> Tensor:
+    """The torch form of ops.lora_linear (CPU path and reference)."""
+    import sys
+
+    p = float(p) if training else 0.0
+    if p > 0.0 and seed is None:
+        seed = int(torch.randint(0, 2**31 - 1, (1,)).item())
+    return LoRALinearFn.apply(x, weight, bias, lora_a, lora_b,
+                              float(scaling), p, int(seed or 0),
+                              sys.modules[__name__])

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import os
 import re
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence
 
 import torch
 
@@ -122,6 +122,7 @@ def _pack_rows(input_ids: List[List[int]], labels: List[List[int]],
     }
 
 
+LORA_IMPLEMENTATIONS = (None, "genrec")
 SEM_ID_RE = re.compile(r"<C(\d+)_(\d+)>")
 
 
@@ -312,7 +313,21 @@ def train(
     # None = evaluation prefills the left-padded prompts; "packed" = it
     # drops the pads (needs beam_cache="shared_prefix")
     prefill: Optional[str] = None,
+    # with use_lora: None = peft when importable (else the full model);
+    # "genrec" = the project's adapters on the fused lora kernels, with the
+    # reference trainer's defaults (all seven Qwen2 projections)
+    lora_implementation: Optional[str] = None,
+    lora_r: int = 16,
+    lora_alpha: float = 32,
+    lora_dropout: float = 0.05,
+    lora_target_modules: Optional[Sequence[str]] = None,
+    lora_modules_to_save: Sequence[str] = (),
 ):
+    if use_lora and lora_implementation not in LORA_IMPLEMENTATIONS:
+        raise ValueError(
+            f"lora_implementation {lora_implementation!r}: expected one of "
+            f"{LORA_IMPLEMENTATIONS}")
+    native_lora = use_lora and lora_implementation == "genrec"
     if max_length is not None:
         max_seq_len = max_length
     if num_codebooks is not None:
@@ -339,7 +354,15 @@ def train(
     model.add_codebook_tokens(n_codebooks, codebook_size)
     if checkpoint_path and os.path.isdir(checkpoint_path):
         model.load_pretrained(checkpoint_path)
-    if use_lora:
+    if native_lora:
+        n_wrapped = model.apply_lora(
+            r=lora_r, alpha=lora_alpha, dropout=lora_dropout,
+            target_modules=lora_target_modules,
+            modules_to_save=tuple(lora_modules_to_save))
+        logger.info("LoRA: %d adapted linears, %d trainable parameters",
+                    n_wrapped, sum(p.numel() for p in model.parameters()
+                                   if p.requires_grad))
+    elif use_lora:
         try:
             from peft import LoraConfig, get_peft_model
 
@@ -385,7 +408,9 @@ def train(
         wb.finish()
         return metrics
 
-    opt = torch.optim.AdamW(model.parameters(), lr=learning_rate,
+    opt_params = [p for p in model.parameters() if p.requires_grad] \
+        if native_lora else model.parameters()
+    opt = torch.optim.AdamW(opt_params, lr=learning_rate,
                             weight_decay=weight_decay)
     steps_per_epoch = max(1, len(train_loader) // gradient_accumulate_every)
     if warmup_ratio is not None:

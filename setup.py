@@ -33,6 +33,7 @@ sources = [
     "csrc/kernels/attention_beam.hip",
     "csrc/kernels/skinny_gemm.hip",
     "csrc/kernels/llm_layer.hip",
+    "csrc/kernels/lora.hip",
 ]
 
 cxx_flags = ["-O3", "-std=c++17"]
