@@ -57,6 +57,18 @@ std::vector<torch::Tensor> hstu_attn_bwd(
     torch::Tensor s_saved, torch::Tensor pos_bucket,
     c10::optional<torch::Tensor> timestamps,
     int64_t n_pos, int64_t n_time);
+torch::Tensor hstu_attn_flash_fwd(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    torch::Tensor rel_bucket, torch::Tensor pos_table,
+    c10::optional<torch::Tensor> time_table,
+    c10::optional<torch::Tensor> timestamps,
+    c10::optional<torch::Tensor> key_pad);
+std::vector<torch::Tensor> hstu_attn_flash_bwd(
+    torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    torch::Tensor rel_bucket, torch::Tensor pos_table,
+    c10::optional<torch::Tensor> time_table,
+    c10::optional<torch::Tensor> timestamps,
+    c10::optional<torch::Tensor> key_pad);
 
 std::vector<torch::Tensor> softmax_ce_fwd(torch::Tensor logits,
                                           torch::Tensor targets,
@@ -209,6 +221,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("table_mode") = false, py::arg("backward") = false);
   m.def("hstu_attn_fwd", &genrec::hstu_attn_fwd, "HSTU fused attention fwd");
   m.def("hstu_attn_bwd", &genrec::hstu_attn_bwd, "HSTU fused attention bwd");
+  m.def("hstu_attn_flash_fwd", &genrec::hstu_attn_flash_fwd,
+        "tiled HSTU attention fwd (any L): out as a [B,H,L,D] view of "
+        "[B,L,H,D] memory");
+  m.def("hstu_attn_flash_bwd", &genrec::hstu_attn_flash_bwd,
+        "tiled HSTU attention bwd: dq, dk, dv, dpos, dtime");
   m.def("softmax_ce_fwd", &genrec::softmax_ce_fwd, "fused CE forward");
   m.def("softmax_ce_bwd", &genrec::softmax_ce_bwd, "fused CE backward");
   m.def("lce_inplace", &genrec::lce_inplace,

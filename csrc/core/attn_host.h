@@ -1,6 +1,7 @@
 // Host-side helpers shared by the flash_strip.h kernels' launch code
-// (attention_gqa, attention_beam, attention_flash, hstu_attn): head-dim
-// dispatch, the stride predicate, operand views and pointer casts.
+// (attention_gqa, attention_beam, attention_flash, hstu_attn,
+// hstu_attn_flash): head-dim dispatch, the stride predicate, operand views
+// and pointer casts.
 #pragma once
 
 #include <torch/extension.h>

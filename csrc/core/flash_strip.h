@@ -1,5 +1,6 @@
 // Strip-level steps of a flash-attention tile, one level above mfma_tile.h
-// (attention_gqa, attention_beam, attention_flash, hstu_attn).
+// (attention_gqa, attention_beam, attention_flash, hstu_attn,
+// hstu_attn_flash).
 //
 // A block of four waves works on 64-row tiles; a wave owns a strip of 16
 // tile rows and holds, per 16-column fragment f, the C fragment
@@ -9,10 +10,10 @@
 // masking, the guarded running softmax, the P stash, the row store of a
 // finished strip, and the stashes and products of a backward tile. The head
 // dim D and every row stride are compile-time for attention_gqa and
-// attention_beam; attention_flash and hstu_attn take D (32 or 64) as a
-// kernel argument and use the runtime forms, all on [4] accumulators and
-// 128-byte rows. Staging, barriers and what a kernel iterates over stay
-// with the kernel.
+// attention_beam; attention_flash, hstu_attn and hstu_attn_flash take D (32
+// or 64) as a kernel argument and use the runtime forms, all on [4]
+// accumulators and 128-byte rows. Staging, barriers and what a kernel
+// iterates over stay with the kernel.
 //
 // Bit-stability: every accumulator here is summed in one fixed order (f
 // outer, kk inner; the reductions as written), so two kernels that call

@@ -21,17 +21,9 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "../core/attn_host.h"
+#include "../core/hstu_bias.h"
 
 namespace genrec {
-
-__device__ __forceinline__ int time_bucket(long long ti, long long tj,
-                                           int n_buckets) {
-  long long diff = ti - tj;
-  if (diff < 0) diff = -diff;
-  if (diff < 1) diff = 1;
-  int b = (int)(__logf((float)diff) / 0.693f);
-  return min(max(b, 0), n_buckets - 1);
-}
 
 __global__ void __launch_bounds__(256)
 hstu_attn_fwd_kernel(

@@ -55,11 +55,14 @@ class SyntheticSeqDataset(Dataset):
     def __init__(self, num_users: int = 2000, num_items: int = 12101,
                  mean_len: float = 8.9, max_seq_len: int = 50,
                  split: str = "train", seed: int = 0,
-                 with_timestamps: bool = False) -> None:
+                 with_timestamps: bool = False, max_len: int = 50) -> None:
+        """max_len: longest per-user sequence generated; raise it together
+        with mean_len for histories that fill a max_seq_len beyond 50."""
         self.num_items = num_items
         self.max_seq_len = max_seq_len
         self.with_timestamps = with_timestamps
-        seqs = _zipf_sequences(num_users, num_items, mean_len, seed)
+        seqs = _zipf_sequences(num_users, num_items, mean_len, seed,
+                               max_len=max_len)
         base_ts = 1_400_000_000
         self.samples: List[Dict] = []
         for u, full in enumerate(seqs):

@@ -29,6 +29,11 @@ from genrec_amd.ops.linear import SplitKLinear
 from genrec_amd.config import ginlite
 
 
+# Up to this length a layer keeps the one-tile kernel and its bias-tensor
+# fallback, bit for bit; beyond it attention goes through ops.hstu_attention.
+ONE_TILE_MAX = 64
+
+
 class RelativePositionBias(nn.Module):
     """T5-style half-exact / half-log bucketed position bias
     (ref hstu.py:283-349)."""
@@ -60,6 +65,18 @@ class RelativePositionBias(nn.Module):
         if buckets is None:
             pos = torch.arange(seq_len, device=device)
             buckets = self._bucket(pos.unsqueeze(0) - pos.unsqueeze(1))
+            self._bucket_cache[key] = buckets
+        return buckets
+
+    def rel_bucket_table(self, seq_len: int, device) -> Tensor:
+        """int32 [2L-1]: bucket_table is Toeplitz, entry [i][j] is
+        rel_bucket_table[j - i + L - 1]. What ops.hstu_attention takes, so
+        that long sequences need no [L,L] table."""
+        key = ("rel", seq_len, str(device))
+        buckets = self._bucket_cache.get(key)
+        if buckets is None:
+            rel = torch.arange(-(seq_len - 1), seq_len, device=device)
+            buckets = self._bucket(rel).to(torch.int32)
             self._bucket_cache[key] = buckets
         return buckets
 
@@ -122,19 +139,29 @@ class HSTULayer(nn.Module):
 
         q, k, v = split(q), split(k), split(v)
         use_time = self.use_temporal_bias and timestamps is not None
-        # fully-fused path: bias bucketing + gathers + SiLU attention in
-        # one MFMA kernel (falls through to the bias-tensor composition)
-        attn = ops.hstu_fused_attention(
-            q, k, v, self.position_bias.bucket_table(l, x.device),
-            self.position_bias.relative_attention_bias.weight,
-            self.temporal_bias.temporal_attention_bias.weight
-            if use_time else None,
-            timestamps if use_time else None, padding_mask)
-        if attn is None:
-            pos_bias = self.position_bias(l, x.device)  # [H, L, L]
-            time_bias = self.temporal_bias(timestamps) if use_time else None
-            attn = ops.hstu_pointwise_attention(q, k, v, pos_bias, time_bias,
-                                                padding_mask)
+        pos_weight = self.position_bias.relative_attention_bias.weight
+        time_weight = self.temporal_bias.temporal_attention_bias.weight \
+            if use_time else None
+        if l > ONE_TILE_MAX:
+            # long sequences: tiled kernel (or the blocked eager op), no
+            # [L,L] bucket table and no [B,H,L,L] bias tensor
+            attn = ops.hstu_attention(
+                q, k, v, self.position_bias.rel_bucket_table(l, x.device),
+                pos_weight, time_weight, timestamps if use_time else None,
+                padding_mask)
+        else:
+            # one tile: bias bucketing + gathers + SiLU attention in one
+            # MFMA kernel (falls through to the bias-tensor composition)
+            attn = ops.hstu_fused_attention(
+                q, k, v, self.position_bias.bucket_table(l, x.device),
+                pos_weight, time_weight, timestamps if use_time else None,
+                padding_mask)
+            if attn is None:
+                pos_bias = self.position_bias(l, x.device)  # [H, L, L]
+                time_bias = self.temporal_bias(timestamps) if use_time \
+                    else None
+                attn = ops.hstu_pointwise_attention(q, k, v, pos_bias,
+                                                    time_bias, padding_mask)
         attn = attn.transpose(1, 2).reshape(b, l, d)
         attn = self.attn_norm(attn) * u
         # replay-safe genrec dropout (hipGraph hazard ledger, BACKLOG)

@@ -86,6 +86,8 @@ from genrec_amd.ops.attention import (  # noqa: E402
     packed_qkv_eligible,
     hstu_pointwise_attention,
     hstu_fused_attention,
+    hstu_attention,
+    hstu_flash_supported,
     gqa_flash_attention,
     gqa_varlen_attention,
     gqa_varlen_supported,
@@ -125,6 +127,8 @@ __all__ = [
     "packed_qkv_eligible",
     "hstu_pointwise_attention",
     "hstu_fused_attention",
+    "hstu_attention",
+    "hstu_flash_supported",
     "gqa_flash_attention",
     "gqa_varlen_attention",
     "gqa_varlen_supported",

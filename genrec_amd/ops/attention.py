@@ -498,6 +498,128 @@ def hstu_fused_attention(q, k, v, pos_bucket, pos_weight, time_weight,
     return None  # caller composes the bias-tensor path
 
 
+class _HstuFlashAttnFn(torch.autograd.Function):
+    """Tiled HSTU attention (csrc/kernels/hstu_attn_flash.hip): saves only
+    its inputs; backward recomputes the scores per tile, so nothing of
+    size L x L exists forward or backward."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, pos_weight, time_weight, rel_bucket,
+                timestamps, key_pad):
+        from genrec_amd import ops
+
+        # The kernel reads bf16 tables. Under autocast the parameters are
+        # fp32: they are rounded here, as autocast rounds a weight, and
+        # their gradients go back in the parameters' dtype.
+        pos_w = pos_weight.to(torch.bfloat16).contiguous()
+        time_w = time_weight.to(torch.bfloat16).contiguous() \
+            if time_weight is not None else None
+        # q/k/v go in as they are: the host copies only what its 16-byte
+        # loads cannot read. out is a [B,H,L,D] view of [B,L,H,D] memory.
+        out = ops.ext().hstu_attn_flash_fwd(q, k, v, rel_bucket, pos_w,
+                                            time_w, timestamps, key_pad)
+        none = torch.empty(0)
+        ctx.save_for_backward(
+            q, k, v, rel_bucket, pos_w,
+            time_w if time_w is not None else none,
+            timestamps if timestamps is not None else none,
+            key_pad if key_pad is not None else none)
+        ctx.dtypes = (pos_weight.dtype,
+                      time_weight.dtype if time_weight is not None else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from genrec_amd import ops
+
+        q, k, v, rel_bucket, pos_w, time_w, ts, key_pad = ctx.saved_tensors
+        use_time = time_w.numel() > 0
+        dq, dk, dv, dpos, dtime = ops.ext().hstu_attn_flash_bwd(
+            dout, q, k, v, rel_bucket, pos_w,
+            time_w if use_time else None, ts if use_time else None,
+            key_pad if key_pad.numel() else None)
+        dpos = dpos.to(ctx.dtypes[0])
+        dtime_out = dtime.to(ctx.dtypes[1]) if use_time else None
+        return dq, dk, dv, dpos, dtime_out, None, None, None
+
+
+# Shortest sequence the tiled kernel takes; up to 64 rows the one-tile
+# kernel of hstu_fused_attention runs.
+HSTU_FLASH_MIN_L = 65
+
+
+def hstu_flash_supported(q: Tensor, k: Tensor, v: Tensor, pos_weight: Tensor,
+                         time_weight: Optional[Tensor] = None) -> bool:
+    """True iff hstu_attention would run the tiled HIP kernel on these
+    inputs (everything on the GPU, bf16 q/k/v, bf16 or fp32 tables (fp32
+    ones, the parameters of a model under autocast, are rounded to bf16 for
+    the kernel), D in {32,64}, L > 64, not disabled)."""
+    if os.environ.get("GENREC_DISABLE_HSTU_FLASH", "0") == "1":
+        return False
+    if not (q.dim() == 4 and k.shape == q.shape and v.shape == q.shape):
+        return False
+    if not (q.dtype == k.dtype == v.dtype == torch.bfloat16):
+        return False
+    tables = (pos_weight,) if time_weight is None \
+        else (pos_weight, time_weight)
+    if any(t.dtype not in (torch.bfloat16, torch.float32) for t in tables):
+        return False
+    if q.size(3) not in (32, 64) or q.size(2) < HSTU_FLASH_MIN_L \
+            or q.size(0) == 0 or q.size(1) == 0:
+        return False
+    return _kernel_available("hstu_attn_flash_fwd", q, k, v, *tables)
+
+
+def hstu_attention(
+    q: Tensor,  # [B, H, L, D]
+    k: Tensor,
+    v: Tensor,
+    rel_bucket: Tensor,                     # [2L-1] int
+    pos_weight: Tensor,                     # [n_pos, H]
+    time_weight: Optional[Tensor] = None,   # [n_time, H]
+    timestamps: Optional[Tensor] = None,    # [B, L] int
+    key_pad_mask: Optional[Tensor] = None,  # [B, L] bool, True = PAD
+) -> Tensor:
+    """HSTU pointwise attention at any sequence length -> [B, H, L, D].
+
+    QK^T (no scale) + position bias + temporal bias, causal and key-pad
+    masks at -1e9, SiLU scores, @ V. The position bucket of (i, j) is
+    rel_bucket[j - i + L - 1] (RelativePositionBias.rel_bucket_table); the
+    time bias is used when time_weight and timestamps are both given. On the
+    GPU, bf16 with D in {32,64} runs the tiled kernel for L > 64 (the result
+    is then a view whose transpose(1,2) is contiguous) and the one-tile
+    kernel of hstu_fused_attention up to 64; everything else is
+    eager.hstu_attention. No [L,L] table is built for L > 64; up to 64 the
+    one-tile kernel's [L,L] table is gathered from rel_bucket on every call
+    (HSTULayer, which caches its bucket_table, does not come this way).
+    rel_bucket, timestamps and key_pad_mask may sit on another device than
+    q; they are moved.
+    """
+    L = q.size(2)
+    if time_weight is None or timestamps is None:
+        time_weight = timestamps = None
+    rel_bucket = rel_bucket.to(q.device)
+    if timestamps is not None:
+        timestamps = timestamps.to(q.device)
+    if key_pad_mask is not None:
+        key_pad_mask = key_pad_mask.to(device=q.device, dtype=torch.bool)
+    if L < HSTU_FLASH_MIN_L and q.is_cuda:
+        pos = torch.arange(L, device=q.device)
+        pos_bucket = rel_bucket[pos[None, :] - pos[:, None] + (L - 1)]
+        out = hstu_fused_attention(q, k, v, pos_bucket, pos_weight,
+                                   time_weight, timestamps, key_pad_mask)
+        if out is not None:
+            return out
+    elif hstu_flash_supported(q, k, v, pos_weight, time_weight):
+        ts = timestamps.contiguous() if timestamps is not None else None
+        kp = key_pad_mask.contiguous() if key_pad_mask is not None else None
+        return _HstuFlashAttnFn.apply(
+            q, k, v, pos_weight, time_weight,
+            rel_bucket.to(torch.int32).contiguous(), ts, kp)
+    return eager.hstu_attention(q, k, v, rel_bucket, pos_weight, time_weight,
+                                timestamps, key_pad_mask)
+
+
 class _GqaFlashAttnFn(torch.autograd.Function):
     """Grouped-query flash attention (csrc/kernels/attention_gqa.hip):
     forward saves only out + lse; backward recomputes S per tile in two

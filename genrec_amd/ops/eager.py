@@ -91,6 +91,81 @@ def fused_attention(
     return torch.matmul(attn, v)
 
 
+def _hstu_rows(qb: Tensor, kf: Tensor, vf: Tensor, rel_bucket: Tensor,
+               pos_w: Tensor, time_w: Optional[Tensor],
+               ts_rows: Optional[Tensor], ts: Optional[Tensor],
+               key_pad_mask: Optional[Tensor], i0: int) -> Tensor:
+    """query rows i0.. of hstu_attention: qb [B,H,n,D] against every key"""
+    n, L = qb.size(2), kf.size(2)
+    i = torch.arange(i0, i0 + n, device=qb.device)[:, None]
+    j = torch.arange(L, device=qb.device)[None, :]
+    scores = torch.matmul(qb, kf.transpose(-2, -1))
+    # The gathers go through fp64 (exact on fp32 values) so that autograd
+    # sums the B*n*L gradient terms of a bucket in fp64: this op is the
+    # oracle of the table gradients, and an fp32 running sum of that length
+    # is off by more than its last digits.
+    bucket = rel_bucket.long()[j - i + (L - 1)]            # [n, L]
+    scores = scores + pos_w.double()[bucket].float().permute(2, 0, 1) \
+        .unsqueeze(0)
+    if time_w is not None:
+        diff = ts_rows.unsqueeze(2) - ts.unsqueeze(1)      # [B, n, L]
+        tb = (torch.log(diff.abs().clamp(min=1).float()) / 0.693).long() \
+            .clamp(min=0, max=time_w.size(0) - 1)
+        scores = scores + time_w.double()[tb].float().permute(0, 3, 1, 2)
+    scores = scores.masked_fill(j > i, NEG_BIG)
+    if key_pad_mask is not None:
+        scores = scores.masked_fill(key_pad_mask[:, None, None, :], NEG_BIG)
+    return torch.matmul(F.silu(scores), vf)
+
+
+def hstu_attention(
+    q: Tensor,  # [B, H, L, D]
+    k: Tensor,
+    v: Tensor,
+    rel_bucket: Tensor,                     # [2L-1] int: bucket of j - i + L - 1
+    pos_weight: Tensor,                     # [n_pos, H]
+    time_weight: Optional[Tensor] = None,   # [n_time, H]
+    timestamps: Optional[Tensor] = None,    # [B, L] int
+    key_pad_mask: Optional[Tensor] = None,  # [B, L] bool, True = PAD
+    *,
+    block: int = 128,
+) -> Tensor:
+    """HSTU pointwise attention, fp32 math -> [B, H, L, D] in q's dtype.
+
+    What hstu_pointwise_attention computes on the materialised biases
+    (ref hstu.py:232-276): QK^T (no scale) + position bias + temporal bias,
+    causal and key-pad masks at -1e9, SiLU, @ V; the position bucket of
+    (i, j) is rel_bucket[j - i + L - 1] and the time bucket the ln2 bucket
+    of |ts_i - ts_j|. Computed `block` query rows at a time, each block
+    recomputed in backward, so no [B,H,L,L] tensor exists: peak memory is
+    O(B*H*block*L) with or without autograd.
+    """
+    from torch.utils.checkpoint import checkpoint
+
+    L = q.size(2)
+    if rel_bucket.numel() != 2 * L - 1:
+        raise ValueError(f"rel_bucket has {rel_bucket.numel()} entries, "
+                         f"needs 2L-1 = {2 * L - 1}")
+    use_time = time_weight is not None and timestamps is not None
+    qf, kf, vf = q.float(), k.float(), v.float()
+    pos_w = pos_weight.float()
+    time_w = time_weight.float() if use_time else None
+    ts = timestamps if use_time else None
+    recompute = torch.is_grad_enabled() and any(
+        t is not None and t.requires_grad
+        for t in (q, k, v, pos_weight, time_weight))
+    outs = []
+    for i0 in range(0, L, block):
+        args = (qf[:, :, i0:i0 + block], kf, vf, rel_bucket, pos_w, time_w,
+                ts[:, i0:i0 + block] if use_time else None, ts, key_pad_mask,
+                i0)
+        if recompute:
+            outs.append(checkpoint(_hstu_rows, *args, use_reentrant=False))
+        else:
+            outs.append(_hstu_rows(*args))
+    return torch.cat(outs, dim=2).to(q.dtype)
+
+
 def gqa_attention(
     q: Tensor,  # [B, Hq, Lq, D]
     k: Tensor,  # [B, Hkv, Lk, D]

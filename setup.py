@@ -21,6 +21,7 @@ sources = [
     "csrc/kernels/attention.hip",
     "csrc/kernels/attention_mfma.hip",
     "csrc/kernels/hstu_attn.hip",
+    "csrc/kernels/hstu_attn_flash.hip",
     "csrc/kernels/ce.hip",
     "csrc/kernels/linear_ce.hip",
     "csrc/kernels/quantize.hip",
